@@ -11,13 +11,24 @@ configs[1]: Llama-3-8B QSpec, k=3, bs=4, synthetic weights and prompts (SURVEY.m
 the timed region (inputs resident in HBM when timing starts).
 
 One JSON line on rank 0.  The hardware quantity is `ms_per_step` (one cycle; identical with the synthetic knob on or
-off): the --steps region is timed `--repeats` (3) times, every repeat from the SAME sequence state (context lengths, tokens, RNG
-state restored: the repeats are the same work), and the MEDIAN region is reported, every region listed in `ms_per_step_repeats`.  With N = 1 and the default workload the line also carries `other_configs`: the other BASELINE.json
-configs' shapes (k=5 bs=32; Llama-2-13B; Llama-3-70B; TinyLlama) built, timed the same way and freed one after the other on
-this GPU, each with its own `ms_per_step`, `value` and dominant-kernel `roofline`.  `value` = emitted tokens per second of the whole job at the SYNTHETIC draft/target agreement named in
+off).  `value` = emitted tokens per second of the whole job at the SYNTHETIC draft/target agreement named in
 `config.agreement` (random int4 weights agree ~1-4 %; the reference's trained checkpoint 0.96; SURVEY.md 8d
-sanctions the controlled-agreement mode) -- the same cycles at the weights' own agreement are under `natural_agreement`,
-and `e2e_incl_prefill` is the demo.py:139-160 figure (prompt pass + decode to max_tokens, tokens / wall time).  Plus
+sanctions the controlled-agreement mode).
+
+A plain run does only what that line needs: set up, `--warmup` untimed cycles, ONE timed region of exactly `--steps` cycles,
+`--dump-outputs DIR` if given, the line.  `--dump-outputs DIR` writes what the timed path computed in its last cycle, as a
+caller of the engine receives it (the cycle's output tokens, the accept mask, every generated token, the sequence lengths,
+and the draft / target probabilities behind them), as DIR/<name>.npy in float32 / float64 (at most 64 MB: a fixed,
+seeded sample of an array that does not fit, its flat indices beside it).  Same arguments = same inputs (seeded weights,
+prompts and sampler), so two builds can be compared output for output.
+
+`--full` adds every other measurement, each a run of its own: the --steps region timed `--repeats` (3) times, every repeat
+from the SAME sequence state (context lengths, tokens, RNG state restored: the repeats are the same work), the MEDIAN
+region reported and every region listed in `ms_per_step_repeats`; with N = 1 and the default workload `other_configs`: the
+other BASELINE.json configs' shapes (k=5 bs=32; Llama-2-13B; Llama-3-70B; TinyLlama) built, timed the same way and freed
+one after the other on this GPU, each with its own `ms_per_step`, `value` and dominant-kernel `roofline`; the same cycles at
+the weights' own agreement under `natural_agreement`; `e2e_incl_prefill`, the demo.py:139-160 figure (prompt pass + decode
+to max_tokens, tokens / wall time); under TP the verify forward of both plans (`config.tp_verify_forward`).  Plus
   roofline      dominant kernel (the W4A4 weight-streaming GEMM): algorithmic bytes / measured launch time
   cpu_baseline  the CPU oracle ("port" of the reference arithmetic) timed on this host's cores on a bounded sample
 
@@ -46,6 +57,11 @@ def parse():
     p.add_argument("--batch", type=int, default=4)
     p.add_argument("--prompt-len", type=int, default=512)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--full", action="store_true",
+                   help="also run every other measurement (repeats, natural agreement, end to end, roofline, CPU baseline, "
+                        "other configs, TP plans); the options below that name them take effect only with --full")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the timed path computed in its last cycle to DIR/<name>.npy (float32 / float64)")
     p.add_argument("--lm-head-std", type=float, default=0.02)
     p.add_argument("--agreement", default="0.96",
                    help="synthetic draft/target agreement rate of the headline run (random weights agree ~4%%, the "
@@ -57,8 +73,8 @@ def parse():
     p.add_argument("--cpu-cycles", type=int, default=5, help="timed CPU cycles (median), after --cpu-warmup untimed ones")
     p.add_argument("--cpu-warmup", type=int, default=2)
     p.add_argument("--e2e-max-tokens", type=int, default=256, help="max_tokens of the end-to-end (prefill included) run; 0 = skip")
-    p.add_argument("--repeats", type=int, default=3, help="the --steps region is timed this many times back to back; "
-                   "ms_per_step / value are the MEDIAN repeat, every repeat is listed beside them")
+    p.add_argument("--repeats", type=int, default=3, help="--full: the --steps region is timed this many times back to "
+                   "back; ms_per_step / value are the MEDIAN repeat, every repeat is listed beside them (a plain run: 1)")
     p.add_argument("--other-configs", default="auto",
                    help="'auto' (N = 1, default workload only): after the headline also time the other BASELINE.json configs' shapes "
                         "on this GPU and report them under other_configs; 'none' = skip; or a list 'model:k:batch,...'")
@@ -449,6 +465,38 @@ def median_region(regions):
     return regions[order[len(order) // 2]]
 
 
+DUMP_FULL_MAX = 4 << 20      # elements: an array up to this size is written whole ...
+DUMP_SAMPLE = 2 << 20        # ... a larger one as this many elements at fixed, seeded flat indices (<name>_index.npy)
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what the timed path computed in its last cycle, as a caller of the engine receives it --
+    read_outputs()'s tokens [B, k+1] (-1 = not emitted), the accept mask [B, k], generated() as a [B, max_new] table
+    (-1 beyond gen_lens) with the lengths, and the draft / target probabilities the rejection sampler decided on.
+    Integers go out as float64 (exact), probabilities as float32.  Returns {name: shape} of what was written."""
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {"out_tokens": (eng.out_tokens, np.float64), "accepted": (eng.accepted, np.float32),
+              "gen_tokens": (eng.gen_tokens, np.float64), "gen_lens": (eng.gen_lens, np.float64),
+              "seq_lens": (eng.seq_lens, np.float64),
+              "draft_probs": (eng.draft_probs_kbv.transpose(0, 1), np.float32),     # [B, k, V]
+              "target_probs": (eng.target_probs, np.float32)}                        # [B, k+1, V]
+    os.makedirs(out_dir, exist_ok=True)
+    written, total = {}, 0
+    for name, (t, dt) in arrays.items():
+        a = t.detach().cpu().numpy().astype(dt)
+        if a.size > DUMP_FULL_MAX:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+            np.save(os.path.join(out_dir, name + "_index.npy"), idx.astype(np.float64))
+            total += idx.size * 8
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+        written[name] = list(a.shape)
+    assert total <= 64_000_000, total
+    return written
+
+
 def roofline_block(model, eng, cfg, batch, k):
     tot_b, tot_t, n, per_shape = measure_dominant_kernel(model, eng)
     achieved = tot_b / tot_t / 1e9
@@ -566,7 +614,10 @@ def main():
         gc.collect()
         return total / dt, t_prefill, cycles, dt
 
-    eng, regions = run(rho, args.warmup, args.steps, max(1, args.repeats))
+    # a plain run times the --steps region once; --full repeats it from the same state and reports the median
+    eng, regions = run(rho, args.warmup, args.steps, max(1, args.repeats) if args.full else 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)
     dt, acc, emit, draft = median_region(regions)     # ms_per_step / value: the MEDIAN of the timed regions
     per_step = [r[0] / args.steps * 1e3 for r in regions]
     rate = acc / draft if draft else float("nan")
@@ -608,7 +659,8 @@ def main():
         "accepted_tokens": acc, "emitted_tokens": emit, "draft_tokens": draft,
     }
     out.update(cycle_numbers(cfg, args.k, args.batch, dt / args.steps))
-    if rho is not None and args.natural_steps > 0:
+    # ---- everything below is a measurement of its own: --full only
+    if args.full and rho is not None and args.natural_steps > 0:
         # the same engine code with the random weights' own agreement (acceptance ~ a few %): reported beside the headline
         _, reg2 = run(None, min(args.warmup, 5), args.natural_steps)
         dt2, acc2, emit2, draft2 = reg2[0]
@@ -616,25 +668,25 @@ def main():
                                     "ms_per_step": round(dt2 / args.natural_steps * 1e3, 4),
                                     "draft_acceptance_rate": round(acc2 / draft2, 4) if draft2 else None,
                                     "system_efficiency": round(emit2 / ((draft2 // args.k) * (args.k + 1)), 4) if draft2 else None}
-    if args.e2e_max_tokens > 0:
+    if args.full and args.e2e_max_tokens > 0:
         tps, t_pre, cycles, wall = run_e2e(rho, args.e2e_max_tokens)
         out["e2e_incl_prefill"] = {"value": round(tps, 2), "unit": "tokens/s", "max_tokens": args.e2e_max_tokens,
                                    "prompt_tokens": args.batch * args.prompt_len, "prefill_ms": round(t_pre * 1e3, 2),
                                    "cycles": cycles, "wall_s": round(wall, 4),
                                    "what": "demo.py:139-160: generated tokens / (prompt pass + decode) wall time, requests "
                                            "leave the batch at max_tokens"}
-    if world > 1:
+    if args.full and world > 1:
         out["config"]["tp_verify_forward"] = measure_verify_plans(model, eng, world)
-    if rank == 0 and not args.no_roofline:   # the draft pass is replicated under TP: rank 0's launches are every rank's
+    if args.full and rank == 0 and not args.no_roofline:   # the draft pass is replicated under TP: rank 0's launches are every rank's
         out["roofline"] = roofline_block(model, eng, cfg, args.batch, args.k)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(model, args, rho)
-    # ---- the other BASELINE.json configs on this GPU (N = 1, default workload only: the driver's run)
+    # ---- the other BASELINE.json configs on this GPU (N = 1, default workload only)
     others = []
-    if args.other_configs == "auto":
+    if args.full and args.other_configs == "auto":
         if world == 1 and (args.model, args.k, args.batch) == ("llama-3-8b", 3, 4):
             others = list(OTHER_CONFIGS)
-    elif args.other_configs not in ("none", ""):
+    elif args.full and args.other_configs not in ("none", ""):
         for item in args.other_configs.split(","):
             nm, kk, bb = item.split(":")
             others.append((nm, int(kk), int(bb), f"{nm} k={kk} bs={bb}"))

@@ -327,7 +327,7 @@ def test_batch32_draft_forms_vs_oracle(ops, oracle, M):
 
 def _experimental_lib():
     """libqspec_hip_experimental.so (make -C qspec_amd/csrc experimental): the measured-and-rejected variants and the dev knobs
-    live only there since round 4; the product library has neither.  Not built by __graft_entry__.build()."""
+    live only there since round 4; the product library has neither.  Built by __graft_entry__.build()."""
     from qspec_amd import _lib
     return _lib.EXPERIMENTAL_LIB_PATH
 
