@@ -258,7 +258,7 @@ def test_w4a4_gemm_golden(ops, golden_dir):
 def assert_close_1e3(got, ref):
     got, ref = got.astype(np.float64), ref.astype(np.float64)
     tol = 1e-3 * np.maximum(1.0, np.abs(ref))
-    bad = np.abs(got - ref) > tol
+    bad = ~(np.abs(got - ref) <= tol)   # NaN / inf in either fails (a plain `> tol` lets NaN through)
     assert not bad.any(), (np.abs(got - ref).max(), int(bad.sum()))
 
 
@@ -301,13 +301,27 @@ def test_both_views_read_the_same_buffer(ops, oracle):
     assert torch.equal(w, before)
 
 
-@pytest.mark.parametrize("M,w4a4,d", [(4, True, 128), (16, True, 128), (33, True, 128), (16, False, 128), (24, False, 128),
-                                      (1, True, 64), (4, True, 64), (16, True, 64), (24, True, 64), (4, False, 64), (16, False, 64)])
+QKV_ROPE_SHAPES = [(4, True, 128), (16, True, 128), (33, True, 128), (16, False, 128), (24, False, 128),
+                   (1, True, 64), (4, True, 64), (16, True, 64), (24, True, 64), (4, False, 64), (16, False, 64)]
+
+
+@pytest.mark.parametrize("M,w4a4,d", QKV_ROPE_SHAPES)
 def test_qkv_rope_linear_equals_gemm_then_rope_then_cache(ops, oracle, M, w4a4, d):
+    _qkv_rope_linear_check(ops, oracle, M, w4a4, d, 16)
+
+
+@pytest.mark.parametrize("bs", [8, 32])
+@pytest.mark.parametrize("M,w4a4,d", QKV_ROPE_SHAPES)
+def test_qkv_rope_linear_equals_gemm_then_rope_then_cache_block_sizes(ops, oracle, M, w4a4, d, bs):
+    """The same at vLLM's other common KV block sizes (the same data: 1024 cache slots at every block size)."""
+    _qkv_rope_linear_check(ops, oracle, M, w4a4, d, bs)
+
+
+def _qkv_rope_linear_check(ops, oracle, M, w4a4, d, bs):
     """Fused epilogue == the three reference ops one after the other, bit for bit (same kernels' arithmetic).  Head size 64
     (TinyLlama: 32 + 2 x 4 heads, K = 2048) runs on the streaming kernels only (RoPE pairs (i, i + 32), four tiles per head)."""
     rng = np.random.default_rng(M)
-    nq, nkv, K, bs = (8, 2, 1024, 16) if d == 128 else (32, 4, 2048, 16)
+    nq, nkv, K = (8, 2, 1024) if d == 128 else (32, 4, 2048)
     N = (nq + 2 * nkv) * d
     if not ops.qkv_rope_linear_supported(w4a4, M, N, K, d):   # head size 64 beyond the streaming shapes: refused, not mis-computed
         assert d == 64 and M > 16
@@ -322,7 +336,7 @@ def test_qkv_rope_linear_equals_gemm_then_rope_then_cache(ops, oracle, M, w4a4, 
     ws = dev((rng.random(N) * 0.01 + 0.001).astype(np.float16))
     cs = dev(oracle.make_cos_sin_cache(d, 2048, 10000.0))
     pos = dev(rng.integers(0, 2048, M).astype(np.int64))
-    slots_np = rng.permutation(64 * bs)[:M].astype(np.int64)
+    slots_np = rng.permutation(1024)[:M].astype(np.int64)   # 1024 slots (and the same data) at every block size
     slots_np[0] = -1
     slots = dev(slots_np)
     if w4a4:
@@ -334,7 +348,7 @@ def test_qkv_rope_linear_equals_gemm_then_rope_then_cache(ops, oracle, M, w4a4, 
         ops.rowwise_scaled_linear_cutlass_s4s4_unified(x, xs, wq, ws, None, ref)
     else:
         ops.w4a16_linear(x, wq, ws, ref)
-    kc0 = torch.zeros(64, bs, nkv, d, dtype=torch.float16, device=DEV); vc0 = torch.zeros_like(kc0)
+    kc0 = torch.zeros(1024 // bs, bs, nkv, d, dtype=torch.float16, device=DEV); vc0 = torch.zeros_like(kc0)
     ops.rope_kv_write(pos, ref, cs, kc0, vc0, slots, nq, nkv, d)
     out = torch.empty_like(ref)
     kc1 = torch.zeros_like(kc0); vc1 = torch.zeros_like(kc0)
@@ -618,8 +632,17 @@ def make_paged(rng, n_seqs, ctx_lens, nkv, d, block_size):
 
 
 def test_rope_and_cache_write_bit_exact(ops, oracle):
+    _rope_and_cache_write_check(ops, oracle, 16)
+
+
+@pytest.mark.parametrize("bs", [8, 32])
+def test_rope_and_cache_write_bit_exact_block_sizes(ops, oracle, bs):
+    _rope_and_cache_write_check(ops, oracle, bs)
+
+
+def _rope_and_cache_write_check(ops, oracle, bs):
     rng = np.random.default_rng(11)
-    T, nq, nkv, d, bs = 6, 32, 8, 128, 16
+    T, nq, nkv, d = 6, 32, 8, 128
     cs = oracle.make_cos_sin_cache(d, 4096, 500000.0)
     pos = rng.integers(0, 4096, T).astype(np.int64)
     qkv = (rng.standard_normal((T, (nq + 2 * nkv) * d))).astype(np.float16)
@@ -629,7 +652,7 @@ def test_rope_and_cache_write_bit_exact(ops, oracle):
     ops.rotary_embedding(dev(pos), t[:, : nq * d], t[:, nq * d:(nq + nkv) * d], d, dev(cs))
     got = host(t)
     assert np.array_equal(bits(got[:, : nq * d]), bits(q0)) and np.array_equal(bits(got[:, nq * d:(nq + nkv) * d]), bits(k0))
-    nb = 8
+    nb = 128 // bs   # 128 slots at every block size (the last one written below)
     kc = torch.zeros(nb, bs, nkv, d, dtype=torch.float16, device=DEV)
     vc = torch.zeros_like(kc)
     slots = np.array([5, 17, 18, -1, 100, 127], np.int64)
@@ -673,11 +696,13 @@ def test_paged_attention_within_1e3(ops, oracle, ctx_lens, q_len, few_splits):
 # ------------------------------------------------------------------ token side
 
 @pytest.mark.parametrize("ctx_lens,q_len,d,nq,nkv", [([37, 200], 1, 64, 32, 4), ([70, 9, 300], 4, 64, 8, 8), ([50], 3, 96, 4, 2),
-                                                     ([1, 600, 1300], 2, 64, 32, 4), ([2100], 1, 64, 8, 4), ([700, 3], 1, 256, 2, 1),
+                                                     ([2, 600, 1300], 2, 64, 32, 4), ([2100], 1, 64, 8, 4), ([700, 3], 1, 256, 2, 1),
                                                      ([300], 4, 8, 4, 4)])
 def test_paged_attention_generic_head_size_within_1e3(ops, oracle, ctx_lens, q_len, d, nq, nkv):
     """Head sizes other than 128 (TinyLlama: 64) take the generic kernel (no context split, no matrix cores): contexts inside
-    and beyond the P.V pass's prefetch window (8 rows per thread), one-key contexts, 1..32 pieces per row."""
+    and beyond the P.V pass's prefetch window (8 rows per thread), one-key rows, 1..32 pieces per row.  (A context holds at
+    least q_len keys: a 1-key context under 2 query tokens put the first query at position -1, a row without keys whose
+    0/0 NaN -- in the kernel and the oracle alike -- the old bar let through.)"""
     rng = np.random.default_rng(sum(ctx_lens) + d)
     bs = 16
     n_seqs = len(ctx_lens)
@@ -1020,11 +1045,21 @@ def test_rejection_sampler_philox_path(ops):
     assert np.array_equal(outs[0][2][rej], tgt[:, :k][rej])
 
 def test_bookkeeping_launches_with_the_embedding_rows(ops):
+    _bookkeeping_with_embedding_check(ops, 16)
+
+
+@pytest.mark.parametrize("bs", [8, 32])
+def test_bookkeeping_launches_with_the_embedding_rows_block_sizes(ops, bs):
+    _bookkeeping_with_embedding_check(ops, bs)
+
+
+def _bookkeeping_with_embedding_check(ops, bs):
     """spec_prepare_draft / spec_advance_draft / spec_prepare_verify with embed=(table, hidden): the same index tensors as the
     plain launches (empty slots, a slot sitting the step out, a row out of blocks included) and hidden[row] = table[token]
     (row 0 for padded rows), i.e. what the plain launch followed by ops.embedding gives -- bit for bit."""
     rng = np.random.default_rng(77)
-    B, k, bs, V, H, max_blocks = 6, 3, 16, 500, 256, 4
+    B, k, V, H = 6, 3, 500, 256
+    max_blocks = 64 // bs   # 64 slots per sequence at every block size
     table = dev((rng.standard_normal((V, H))).astype(np.float16))
     bt = dev(rng.permutation(B * max_blocks).reshape(B, max_blocks).astype(np.int32))
     seq_lens = dev(np.array([37, 0, 5, 63, 64, 20], np.int32))     # slot 1 empty; slot 4: position 63 is its last slot
@@ -1082,10 +1117,19 @@ def test_bookkeeping_launches_with_the_embedding_rows(ops):
 
 
 def test_advance_step(ops, oracle):
+    _advance_step_check(ops, oracle, 16)
+
+
+@pytest.mark.parametrize("bs", [8, 32])
+def test_advance_step_block_sizes(ops, oracle, bs):
+    _advance_step_check(ops, oracle, bs)
+
+
+def _advance_step_check(ops, oracle, bs):
     rng = np.random.default_rng(1)
-    n, bs, mb = 4, 16, 10
+    n, mb = 4, 160 // bs
     bt = rng.integers(0, 1000, (n, mb)).astype(np.int32)
-    seq_lens = np.array([1, 16, 31, 100], np.int32)
+    seq_lens = np.array([1, bs, 2 * bs - 1, 100], np.int32)   # a block's last slot, the next block's first
     sampled = rng.integers(0, 32000, n).astype(np.int64)
     it, pos, sl, sm = np.zeros(n, np.int64), np.zeros(n, np.int64), seq_lens.copy(), np.zeros(n, np.int64)
     oracle.advance_step(it, sampled, pos, sl, sm, bt, bs)
@@ -1712,11 +1756,25 @@ def test_rope_reference_fixture_bit_exact(ops, golden_dir, idx):
 
 
 def test_reshape_and_cache_flash_reference_fixture_bit_exact(ops, golden_dir):
+    _reshape_and_cache_fixture_check(ops, golden_dir, 16)
+
+
+@pytest.mark.parametrize("bs", [8, 32])
+def test_reshape_and_cache_flash_reference_fixture_bit_exact_block_sizes(ops, golden_dir, bs):
+    _reshape_and_cache_fixture_check(ops, golden_dir, bs)
+
+
+def _reshape_and_cache_fixture_check(ops, golden_dir, bs):
+    """The fixture's cache (6 blocks of 16) viewed at block size 8 / 32: a slot is the same row of the flash layout
+    [num_blocks, block_size, n_kv, d] at every block size, so the expected cache is the fixture's, re-viewed."""
     g = np.load(os.path.join(golden_dir, "rope_cache_softmax.npz"))
-    kc, vc = dev(g["cache_key_cache_in"]), dev(g["cache_value_cache_in"])
+    nb, bs0, nkv, d = g["cache_key_cache_in"].shape
+    assert (nb * bs0) % bs == 0
+    view = lambda a: a.reshape(nb * bs0 // bs, bs, nkv, d)  # noqa: E731
+    kc, vc = dev(view(g["cache_key_cache_in"])), dev(view(g["cache_value_cache_in"]))
     ops.reshape_and_cache_flash(dev(g["cache_key"]), dev(g["cache_value"]), kc, vc, dev(g["cache_slot_mapping"]))
-    assert np.array_equal(bits(host(kc)), bits(g["cache_key_cache_out"]))
-    assert np.array_equal(bits(host(vc)), bits(g["cache_value_cache_out"]))
+    assert np.array_equal(bits(host(kc)), bits(view(g["cache_key_cache_out"])))
+    assert np.array_equal(bits(host(vc)), bits(view(g["cache_value_cache_out"])))
 
 
 def test_softmax_argmax_reference_fixture(ops, golden_dir):

@@ -120,7 +120,8 @@ def _rel3(got, ref):
     return np.abs(got - ref) / (1e-3 * np.maximum(1.0, np.abs(ref)))
 
 
-def _engine_cycle_check(model, oracle, k, B, prompt_lens, cycles, seed, tv_bars, sync_kv=False, d_q98=None):
+def _engine_cycle_check(model, oracle, k, B, prompt_lens, cycles, seed, tv_bars, sync_kv=False, d_q98=None, block_size=16,
+                        max_model_len=256):
     """Three full cycles (k=3, B=4).  Two HIP-vs-oracle differences are legitimate: fp32 summation order inside
     attention / the W4A16 MFMA, and (a consequence) a rare different int4 value downstream.  So:
       * numerics: the oracle engine is teacher-forced with the GPU's draft tokens; its draft / target
@@ -133,9 +134,10 @@ def _engine_cycle_check(model, oracle, k, B, prompt_lens, cycles, seed, tv_bars,
     rng = np.random.default_rng(seed)
     V = tiny.config.vocab_size
     prompts = [rng.integers(0, V, n).tolist() for n in prompt_lens]
-    eng = QSpecEngine(tiny, k, B, max_model_len=256, block_size=16, max_new_tokens=64, use_graph=False, seed=0)
+    bs = block_size
+    eng = QSpecEngine(tiny, k, B, max_model_len=max_model_len, block_size=bs, max_new_tokens=64, use_graph=False, seed=0)
     eng.add_sequences(prompts)
-    oe = OracleEngine(OracleModel.from_torch_model(tiny, 16), k, B, 256, 16)
+    oe = OracleEngine(OracleModel.from_torch_model(tiny, bs), k, B, max_model_len, bs)
     oe.add_sequences(prompts)
     # prefill: greedy target token.  The W4A16 prompt pass is 1e-3-close, not bit-identical, so a near-tie of the two
     # best logits may resolve differently: then the oracle must rate the GPU's token within 2 % of its own best, and
@@ -192,7 +194,7 @@ def _engine_cycle_check(model, oracle, k, B, prompt_lens, cycles, seed, tv_bars,
         assert np.array_equal(eng.v_pos.view(B, k + 1).cpu().numpy(), (L0 - 1)[:, None] + np.arange(k + 1)[None])
         bt = eng.block_tables.cpu().numpy()
         pos = eng.v_pos.view(B, k + 1).cpu().numpy()
-        exp_slots = np.take_along_axis(bt, (pos // 16).astype(np.int64), 1).astype(np.int64) * 16 + pos % 16
+        exp_slots = np.take_along_axis(bt, (pos // bs).astype(np.int64), 1).astype(np.int64) * bs + pos % bs
         assert np.array_equal(eng.v_slots.view(B, k + 1).cpu().numpy(), exp_slots)
     # W4A4 is chaotic (a single different int4 can re-scale a row), so the draft distributions are compared
     # statistically: most of them agree to fp32 rounding, none is far off; the W4A16 target must stay close always
@@ -214,11 +216,30 @@ def _engine_cycle_check(model, oracle, k, B, prompt_lens, cycles, seed, tv_bars,
     assert [m.accepted_tokens, m.emitted_tokens, m.draft_tokens] == counters.tolist()
     rate, eff = oracle.spec_metrics(*counters.tolist(), k)
     assert abs(m.draft_acceptance_rate - rate) < 1e-12 and abs(m.system_efficiency - eff) < 1e-12
+    return eng
 
 
 
 def test_engine_cycle_matches_oracle_engine(tiny, oracle):
     _engine_cycle_check(tiny, oracle, 3, 4, (17, 33, 64, 5), 3, 2, (0.12, 0.6, 5e-3, 0.15))
+
+
+@pytest.mark.parametrize("block_size", [8, 32])
+def test_engine_cycle_matches_oracle_engine_block_sizes(tiny, oracle, block_size):
+    """vLLM's other common KV block sizes: the cache writers, the slot bookkeeping and the attention kernels at block size
+    8 (the waves kernel's non-FAST form) and 32, with the bars of test_engine_cycle_matches_oracle_engine."""
+    _engine_cycle_check(tiny, oracle, 3, 4, (17, 33, 64, 5), 3, 2, (0.12, 0.6, 5e-3, 0.15), block_size=block_size)
+
+
+def test_engine_cycle_long_context_wide_block_table(oracle):
+    """max_model_len 4096 at block size 16: a 256-entry block table, wider than the 128 entries the attention kernels hold
+    in registers, so every attention launch -- the prompt pass included -- reads its table from memory (BT = false).  One
+    sequence's prompt ends 3 keys short of 2048 and its verify windows carry it across key 2048."""
+    from qspec_amd.model import QuarotLlamaConfig, QuarotLlamaForCausalLM
+    cfg = QuarotLlamaConfig(1024, 3584, 8, 2, 2, 2048, 1e-5, 10000.0, 4096, "tiny-4k")   # tiny_cfg with 4096 positions
+    model = QuarotLlamaForCausalLM(cfg, DEV).init_synthetic(seed=1, lm_head_std=0.05)
+    eng = _engine_cycle_check(model, oracle, 3, 4, (2045, 33, 64, 5), 3, 2, (0.12, 0.6, 5e-3, 0.15), max_model_len=4096)
+    assert eng.block_tables.shape[1] == 256 and int(eng.seq_lens.max()) > 2048
 
 
 # With the KV history teacher-forced as well (sync_kv) the draft pass starts every cycle on IDENTICAL inputs: its
