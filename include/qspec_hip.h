@@ -409,6 +409,40 @@ int qspec_sample_top_k_top_p(const qspec_half* logits, const float* temperature,
                              const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
                              int64_t* token, int64_t token_stride, int tokens, int vocab, void* workspace, void* stream);
 
+/* Seeded draws: SamplingParams.seed honoured inside the captured cycle (the reference's seeded_seqs,
+ *   vllm/spec_decode/spec_decode_worker.py:295,901-906 -> rejection_sampler.py:60-67,229-250,387-399).
+ *   Per SEQUENCE device arrays, read when the call runs (a captured graph serves changing seeds):
+ *     seq_seeds [nseq] int64, seq_seeded [nseq] int32 (0: the row uses the engine stream exactly as the unseeded entry),
+ *     base_pos [nseq] int32 (the engine passes seq_lens at the start of a cycle / non-speculative step, the prompt length
+ *     for the first token).
+ *   A row of a seeded sequence draws Philox4x32-10 with
+ *     key     = (seed & 0xFFFFFFFF, seed >> 32)
+ *     counter = (c0, 0x80000000 | stream << 16 | j, base_pos, 0)
+ *       c0 = vocab index v (per-token noise) or 0xFFFFFFFF (the accept uniform);
+ *       stream 1 draft sample (j = draft step), 2 target sample (j = verify position 0..k; 0 for the first token and the
+ *       non-speculative step), 3 rejection exponential (j = i), 4 rejection uniform (j = i).
+ *   So its draws depend only on (seed, base_pos, stream, j, v): never on the row or slot, on rng_state or on other rows (the
+ *   top bit of c1 keeps them apart from the engine stream, whose c1 is a row index or 0x40000000 | row).  Rows of unseeded
+ *   sequences draw exactly what the unseeded entry draws, and rng_state (if given) advances as there.
+ *   qspec_sample_top_k_top_p_seeded: row t belongs to sequence t / rows_per_seq with j = j_base + t % rows_per_seq
+ *     (draft step i: rows_per_seq 1, j_base i, draw_stream 1; verify pass: k+1, 0, 2); num_seqs * rows_per_seq >= tokens,
+ *     j_base + rows_per_seq <= 65536.
+ *   qspec_rejection_sample_seeded: sequence b = batch row b (the arrays are [batch]); streams 3 and 4, j = i. */
+int qspec_sample_top_k_top_p_seeded(const qspec_half* logits, const float* temperature, const int32_t* top_k,
+                                    const float* top_p, const float* exponential, uint64_t seed, uint64_t offset,
+                                    uint64_t* rng_state, float* probs, int64_t* token, int64_t token_stride, int tokens,
+                                    int vocab, const int64_t* seq_seeds, const int32_t* seq_seeded, const int32_t* base_pos,
+                                    int num_seqs, int rows_per_seq, int j_base, int draw_stream, void* workspace,
+                                    void* stream);
+int qspec_rejection_sample_seeded(const float* target_with_bonus_probs, const int64_t* bonus_token_ids,
+                                  const float* draft_probs, const int64_t* draft_token_ids, const float* uniform,
+                                  const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, int batch,
+                                  int k, int vocab, int64_t dp_stride_b, int64_t dp_stride_k, int64_t ids_stride_b,
+                                  int64_t ids_stride_k, int64_t bonus_stride,
+                                  int64_t* out_tokens, uint8_t* accepted, int64_t* recovered, int64_t* counters,
+                                  const int32_t* active_lens, const int64_t* seq_seeds, const int32_t* seq_seeded,
+                                  const int32_t* base_pos, void* workspace, void* stream);
+
 /* TypicalAcceptanceSampler.forward(target_with_bonus_probs, bonus_token_ids, draft_probs, draft_token_ids)
  *   vllm/model_executor/layers/typical_acceptance_sampler.py:37-172 (MEDUSA 3.3.1), selected by
  *   draft_token_acceptance_method = "typical_acceptance_sampler" (vllm/spec_decode/spec_decode_worker.py:95-110).

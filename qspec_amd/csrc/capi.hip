@@ -469,6 +469,55 @@ int qspec_sample_top_k_top_p(const qspec_half* logits, const float* temperature,
     return finish(op, qspec::sample_top_k_top_p(CH(logits), temperature, top_k, top_p, exponential, seed, offset, rng_state, probs,
                                                 token, token_stride, tokens, vocab, workspace, ST));
 }
+// Seeded twins of qspec_rejection_sample / qspec_sample_top_k_top_p: rows of a sequence with seq_seeded != 0 draw from
+// Philox keyed by (seed, base position, stream, j, v) alone (include/qspec_hip.h, "seeded draws"); the reference honours
+// SamplingParams.seed through seeded_seqs (vllm/spec_decode/spec_decode_worker.py:295,901-906 ->
+// vllm/model_executor/layers/rejection_sampler.py:60-67,229-250,387-399; Sampler: sampler.py:585-604).
+int qspec_rejection_sample_seeded(const float* target_with_bonus_probs, const int64_t* bonus_token_ids,
+                                  const float* draft_probs, const int64_t* draft_token_ids, const float* uniform,
+                                  const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, int batch,
+                                  int k, int vocab, int64_t dp_stride_b, int64_t dp_stride_k, int64_t ids_stride_b,
+                                  int64_t ids_stride_k, int64_t bonus_stride,
+                                  int64_t* out_tokens, uint8_t* accepted, int64_t* recovered, int64_t* counters,
+                                  const int32_t* active_lens, const int64_t* seq_seeds, const int32_t* seq_seeded,
+                                  const int32_t* base_pos, void* workspace, void* stream) {
+    const char* op = "qspec_rejection_sample_seeded";
+    if (batch == 0) return 0;
+    NONNULL(op, target_with_bonus_probs); NONNULL(op, bonus_token_ids); NONNULL(op, draft_probs);
+    NONNULL(op, draft_token_ids); NONNULL(op, out_tokens); NONNULL(op, accepted); NONNULL(op, recovered);
+    NONNULL(op, seq_seeds); NONNULL(op, seq_seeded); NONNULL(op, base_pos); NONNULL(op, workspace);
+    if (batch < 0) return fail("%s: batch < 0", op);
+    if (batch * k > 4096) return fail("%s: batch*k=%d too large", op, batch * k);
+    if (k < 1) return fail("%s: k=%d must be >= 1", op, k);
+    return finish(op, qspec::rejection_sample_seeded(target_with_bonus_probs, draft_probs, draft_token_ids, bonus_token_ids,
+                                                     uniform, exponential, seed, offset, rng_state, batch, k, vocab, dp_stride_b,
+                                                     dp_stride_k, ids_stride_b, ids_stride_k, bonus_stride, out_tokens, accepted,
+                                                     recovered, counters, active_lens, seq_seeds, seq_seeded, base_pos,
+                                                     workspace, ST));
+}
+int qspec_sample_top_k_top_p_seeded(const qspec_half* logits, const float* temperature, const int32_t* top_k,
+                                    const float* top_p, const float* exponential, uint64_t seed, uint64_t offset,
+                                    uint64_t* rng_state, float* probs, int64_t* token, int64_t token_stride, int tokens,
+                                    int vocab, const int64_t* seq_seeds, const int32_t* seq_seeded, const int32_t* base_pos,
+                                    int num_seqs, int rows_per_seq, int j_base, int draw_stream, void* workspace,
+                                    void* stream) {
+    const char* op = "qspec_sample_top_k_top_p_seeded";
+    if (tokens < 0) return fail("%s: tokens < 0", op);
+    if (tokens == 0) return 0;
+    NONNULL(op, logits); NONNULL(op, probs); NONNULL(op, token); NONNULL(op, workspace);
+    NONNULL(op, seq_seeds); NONNULL(op, seq_seeded); NONNULL(op, base_pos);
+    if (vocab < 1) return fail("%s: vocab < 1", op);
+    if (rows_per_seq < 1) return fail("%s: rows_per_seq=%d must be >= 1", op, rows_per_seq);
+    if ((int64_t)num_seqs * rows_per_seq < tokens)
+        return fail("%s: num_seqs=%d x rows_per_seq=%d does not cover tokens=%d", op, num_seqs, rows_per_seq, tokens);
+    if (j_base < 0 || j_base + rows_per_seq > 65536)
+        return fail("%s: j_base=%d + rows_per_seq=%d outside the 16-bit sub-index", op, j_base, rows_per_seq);
+    if (draw_stream != 1 && draw_stream != 2) return fail("%s: draw_stream=%d must be 1 (draft) or 2 (target)", op, draw_stream);
+    return finish(op, qspec::sample_top_k_top_p_seeded(CH(logits), temperature, top_k, top_p, exponential, seed, offset,
+                                                       rng_state, probs, token, token_stride, tokens, vocab, seq_seeds,
+                                                       seq_seeded, base_pos, num_seqs, rows_per_seq, j_base, draw_stream,
+                                                       workspace, ST));
+}
 int qspec_typical_acceptance_sample(const float* target_with_bonus_probs, const int64_t* bonus_token_ids,
                                     const int64_t* draft_token_ids, float posterior_threshold, float posterior_alpha, int batch,
                                     int k, int vocab, int64_t ids_stride_b, int64_t ids_stride_k, int64_t bonus_stride,

@@ -198,6 +198,33 @@ __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2
 }
 __device__ __forceinline__ float u01_open(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
+// Per-sequence seeded draws (SamplingParams.seed; the reference's seeded_seqs, rejection_sampler.py:60-67,229-250,387-399).
+// A row of a seeded sequence keys its Philox by the request alone (include/qspec_hip.h, "seeded draws"):
+//   key = (seed lo, seed hi), counter = (c0, 0x80000000 | stream << 16 | j, base_pos, 0)
+// c0 = v (per-token noise) or 0xFFFFFFFF (accept uniform).  Rows of unseeded sequences keep the engine stream's
+// (seed, offset) key and counter bit for bit.  Every pointer is read at replay (captured graphs serve changing seeds).
+struct PhiloxKey {
+    uint32_t k0, k1, c1, c2, c3;
+};
+struct SeedRows {
+    const int64_t* seeds;      // [nseq]
+    const int32_t* seeded;     // [nseq], 0 = the engine stream
+    const int32_t* base_pos;   // [nseq]
+    int rows_per_seq;          // row t -> sequence t / rows_per_seq, j = j_base + t % rows_per_seq
+    int j_base;
+    uint32_t stream;           // 1 draft sample, 2 target sample, 3 rejection exponential, 4 rejection uniform
+};
+__device__ __forceinline__ PhiloxKey engine_key(uint64_t seed, uint64_t offset, uint32_t c1) {
+    return PhiloxKey{(uint32_t)seed, (uint32_t)(seed >> 32), c1, (uint32_t)offset, (uint32_t)(offset >> 32)};
+}
+// the key of a row of sequence s at sub-index j: the sequence's own when it is seeded, else `fallback`
+__device__ __forceinline__ PhiloxKey seeded_key(const SeedRows& sr, int s, uint32_t stream, int j, PhiloxKey fallback) {
+    if (!sr.seeded[s]) return fallback;
+    const uint64_t sd = (uint64_t)sr.seeds[s];
+    return PhiloxKey{(uint32_t)sd, (uint32_t)(sd >> 32), 0x80000000u | (stream << 16) | ((uint32_t)j & 0xFFFFu),
+                     (uint32_t)sr.base_pos[s], 0u};
+}
+
 // accepted[b,i] = U < min(1, q[x]/p[x]);
 // recovered[b,i] = argmax_v ( max(q_v - p_v, FLT_MIN) / S ) / E_v ,  S = sum_v max(q_v - p_v, FLT_MIN)
 // target_probs [B, k+1, V], draft_probs (b,i,v) at b*dp_sb + i*dp_sk + v.  uniform [B,k] / exponential [B,k,V] may
@@ -222,12 +249,16 @@ __global__ __launch_bounds__(256) void rejection_sum_kernel(const float* __restr
     s = block_sum_f64(s, red_d);
     if (threadIdx.x == 0) part_s[bk * QS_SM_CHUNKS + c] = s;
 }
+// SEEDED: sequence b of a seeded row draws from its own key (stream 3, j = i); the unseeded instantiation is the
+// engine-stream kernel as it always was
+template <bool SEEDED>
 __global__ __launch_bounds__(256) void rejection_argmax_kernel(const float* __restrict__ target_probs,
                                                                const float* __restrict__ draft_probs,
                                                                const float* __restrict__ exponential, uint64_t seed,
                                                                uint64_t offset, const uint64_t* __restrict__ rng_state,
                                                                int k, int V, int64_t dp_sb, int64_t dp_sk,
-                                                               const double* part_s, SmPartA* __restrict__ part_a) {
+                                                               const double* part_s, SmPartA* __restrict__ part_a,
+                                                               SeedRows sr) {
     __shared__ ArgMax red_a[4];
     const int c = blockIdx.x, bk = blockIdx.y, b = bk / k, i = bk % k;
     int lo, hi;
@@ -238,7 +269,8 @@ __global__ __launch_bounds__(256) void rejection_argmax_kernel(const float* __re
         seed = rng_state[0];
         offset = rng_state[1];
     }
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    PhiloxKey pk = engine_key(seed, offset, (uint32_t)bk);
+    if (SEEDED) pk = seeded_key(sr, b, 3u, i, pk);
     const float tiny = 1.17549435e-38f;
     double tot = 0.0;
     for (int cc = 0; cc < QS_SM_CHUNKS; cc++) tot += part_s[bk * QS_SM_CHUNKS + cc];
@@ -251,7 +283,7 @@ __global__ __launch_bounds__(256) void rejection_argmax_kernel(const float* __re
             e = exponential[(size_t)bk * V + v];
         } else {
             uint32_t r[4];
-            philox4x32((uint32_t)v, (uint32_t)bk, (uint32_t)offset, (uint32_t)(offset >> 32), k0, k1, r);
+            philox4x32((uint32_t)v, pk.c1, pk.c2, pk.c3, pk.k0, pk.k1, r);
             e = -__logf(u01_open(r[0]));
         }
         float val = f / e;
@@ -299,21 +331,22 @@ __device__ __forceinline__ void create_output(int B, int k, const int64_t* __res
     }
 }
 
-// Final step + output assembly + counters; one workgroup.
+// Final step + output assembly + counters; one workgroup.  SEEDED: the accept uniform of a seeded sequence b comes
+// from its own key (stream 4, j = i).
+template <bool SEEDED>
 __global__ __launch_bounds__(1024) void rejection_output_kernel(
     const float* __restrict__ target_probs, const float* __restrict__ draft_probs,
     const int64_t* __restrict__ draft_ids, const int64_t* __restrict__ bonus_ids, const float* __restrict__ uniform,
     uint64_t seed, uint64_t offset, uint64_t* __restrict__ rng_state, const SmPartA* part_a, int B, int k, int V,
     int64_t dp_sb, int64_t dp_sk, int64_t di_sb, int64_t di_sk, int64_t bonus_stride, uint8_t* __restrict__ accepted,
     int64_t* __restrict__ recovered, int64_t* __restrict__ out, int64_t* __restrict__ counters,
-    const int32_t* __restrict__ active_lens) {
+    const int32_t* __restrict__ active_lens, SeedRows sr) {
     // active_lens (may be NULL): row b takes part iff active_lens[b] > 0 (an empty batch slot of the engine emits
     // nothing and is not counted: the reference only ever sees the sequences that are scheduled)
     if (rng_state) {
         seed = rng_state[0];
         offset = rng_state[1];
     }
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     for (int bk = threadIdx.x; bk < B * k; bk += blockDim.x) {
         const int b = bk / k, i = bk % k;
         ArgMax am{-__builtin_inff(), 0x7fffffff};
@@ -326,8 +359,10 @@ __global__ __launch_bounds__(1024) void rejection_output_kernel(
         if (uniform) {
             u = uniform[bk];
         } else {
+            PhiloxKey pk = engine_key(seed, offset, (uint32_t)bk);
+            if (SEEDED) pk = seeded_key(sr, b, 4u, i, pk);
             uint32_t r[4];
-            philox4x32(0xFFFFFFFFu, (uint32_t)bk, (uint32_t)offset, (uint32_t)(offset >> 32), k0, k1, r);
+            philox4x32(0xFFFFFFFFu, pk.c1, pk.c2, pk.c3, pk.k0, pk.k1, r);
             u = (float)(r[0] >> 8) * (1.0f / 16777216.0f);  // [0,1) like torch.rand
         }
         const float qx = target_probs[((size_t)b * (k + 1) + i) * V + x];
@@ -343,23 +378,47 @@ __global__ __launch_bounds__(1024) void rejection_output_kernel(
     if (rng_state && threadIdx.x == 0) rng_state[1] = offset + 1;  // after every draw of this call
 }
 
-int rejection_sample(const float* target_probs, const float* draft_probs, const int64_t* draft_ids,
-                     const int64_t* bonus_ids, const float* uniform, const float* exponential, uint64_t seed,
-                     uint64_t offset, uint64_t* rng_state, int B, int k, int V, int64_t dp_sb, int64_t dp_sk,
-                     int64_t di_sb, int64_t di_sk, int64_t bonus_stride, int64_t* out_tokens, uint8_t* accepted,
-                     int64_t* recovered, int64_t* counters, const int32_t* active_lens, void* ws, hipStream_t st) {
+template <bool SEEDED>
+static int rejection_sample_impl(const float* target_probs, const float* draft_probs, const int64_t* draft_ids,
+                                 const int64_t* bonus_ids, const float* uniform, const float* exponential, uint64_t seed,
+                                 uint64_t offset, uint64_t* rng_state, int B, int k, int V, int64_t dp_sb, int64_t dp_sk,
+                                 int64_t di_sb, int64_t di_sk, int64_t bonus_stride, int64_t* out_tokens, uint8_t* accepted,
+                                 int64_t* recovered, int64_t* counters, const int32_t* active_lens, SeedRows sr, void* ws,
+                                 hipStream_t st) {
     if (B == 0) return 0;
     if (k < 1) return -1;
     SmPartA* part_a = reinterpret_cast<SmPartA*>(ws);
     double* part_s = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + (size_t)B * k * QS_SM_CHUNKS * 8);
     hipLaunchKernelGGL(rejection_sum_kernel, dim3(QS_SM_CHUNKS, B * k), dim3(256), 0, st, target_probs, draft_probs, k,
                        V, dp_sb, dp_sk, part_s);
-    hipLaunchKernelGGL(rejection_argmax_kernel, dim3(QS_SM_CHUNKS, B * k), dim3(256), 0, st, target_probs, draft_probs,
-                       exponential, seed, offset, rng_state, k, V, dp_sb, dp_sk, part_s, part_a);
-    hipLaunchKernelGGL(rejection_output_kernel, dim3(1), dim3(1024), 0, st, target_probs, draft_probs, draft_ids,
+    hipLaunchKernelGGL(rejection_argmax_kernel<SEEDED>, dim3(QS_SM_CHUNKS, B * k), dim3(256), 0, st, target_probs, draft_probs,
+                       exponential, seed, offset, rng_state, k, V, dp_sb, dp_sk, part_s, part_a, sr);
+    hipLaunchKernelGGL(rejection_output_kernel<SEEDED>, dim3(1), dim3(1024), 0, st, target_probs, draft_probs, draft_ids,
                        bonus_ids, uniform, seed, offset, rng_state, part_a, B, k, V, dp_sb, dp_sk, di_sb, di_sk,
-                       bonus_stride, accepted, recovered, out_tokens, counters, active_lens);
+                       bonus_stride, accepted, recovered, out_tokens, counters, active_lens, sr);
     return 0;
+}
+int rejection_sample(const float* target_probs, const float* draft_probs, const int64_t* draft_ids,
+                     const int64_t* bonus_ids, const float* uniform, const float* exponential, uint64_t seed,
+                     uint64_t offset, uint64_t* rng_state, int B, int k, int V, int64_t dp_sb, int64_t dp_sk,
+                     int64_t di_sb, int64_t di_sk, int64_t bonus_stride, int64_t* out_tokens, uint8_t* accepted,
+                     int64_t* recovered, int64_t* counters, const int32_t* active_lens, void* ws, hipStream_t st) {
+    return rejection_sample_impl<false>(target_probs, draft_probs, draft_ids, bonus_ids, uniform, exponential, seed, offset,
+                                        rng_state, B, k, V, dp_sb, dp_sk, di_sb, di_sk, bonus_stride, out_tokens, accepted,
+                                        recovered, counters, active_lens, SeedRows{}, ws, st);
+}
+// sequence b = batch row b: seq_seeds / seq_seeded / base_pos are [B]
+int rejection_sample_seeded(const float* target_probs, const float* draft_probs, const int64_t* draft_ids,
+                            const int64_t* bonus_ids, const float* uniform, const float* exponential, uint64_t seed,
+                            uint64_t offset, uint64_t* rng_state, int B, int k, int V, int64_t dp_sb, int64_t dp_sk,
+                            int64_t di_sb, int64_t di_sk, int64_t bonus_stride, int64_t* out_tokens, uint8_t* accepted,
+                            int64_t* recovered, int64_t* counters, const int32_t* active_lens, const int64_t* seq_seeds,
+                            const int32_t* seq_seeded, const int32_t* base_pos, void* ws, hipStream_t st) {
+    if (!seq_seeds || !seq_seeded || !base_pos) return -1;
+    const SeedRows sr{seq_seeds, seq_seeded, base_pos, 1, 0, 0u};   // (the kernels map (b, i) and the stream themselves)
+    return rejection_sample_impl<true>(target_probs, draft_probs, draft_ids, bonus_ids, uniform, exponential, seed, offset,
+                                       rng_state, B, k, V, dp_sb, dp_sk, di_sb, di_sk, bonus_stride, out_tokens, accepted,
+                                       recovered, counters, active_lens, sr, ws, st);
 }
 
 // ---------------------------------------------------------------- typical acceptance (MEDUSA 3.3.1)
@@ -668,10 +727,12 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(uint32_t* __restrict_
         rows[t] = r;
     }
 }
+// SEEDED: row t of a seeded sequence t / rows_per_seq draws from its own key (sr.stream, j = j_base + t % rows_per_seq)
+template <bool SEEDED>
 __global__ __launch_bounds__(256) void topk_write_kernel(const f16* __restrict__ logits, const TkRow* __restrict__ rows,
                                                          const float* __restrict__ exponential, uint64_t seed, uint64_t offset,
                                                          const uint64_t* __restrict__ rng_state, float* __restrict__ probs,
-                                                         SmPartA* __restrict__ part_a, int V) {
+                                                         SmPartA* __restrict__ part_a, int V, SeedRows sr) {
     __shared__ ArgMax red_a[4];
     const int c = blockIdx.x, t = blockIdx.y;
     int lo, hi;
@@ -681,7 +742,8 @@ __global__ __launch_bounds__(256) void topk_write_kernel(const f16* __restrict__
         seed = rng_state[0];
         offset = rng_state[1];
     }
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    PhiloxKey pk = engine_key(seed, offset, 0x40000000u | (uint32_t)t);
+    if (SEEDED) pk = seeded_key(sr, t / sr.rows_per_seq, sr.stream, sr.j_base + t % sr.rows_per_seq, pk);
     const f16* l = logits + (size_t)t * V;
     float* p = probs + (size_t)t * V;
     ArgMax am{-__builtin_inff(), 0x7fffffff};
@@ -697,7 +759,7 @@ __global__ __launch_bounds__(256) void topk_write_kernel(const f16* __restrict__
                 e = exponential[(size_t)t * V + v];
             } else {
                 uint32_t rr[4];
-                philox4x32((uint32_t)v, 0x40000000u | (uint32_t)t, (uint32_t)offset, (uint32_t)(offset >> 32), k0, k1, rr);
+                philox4x32((uint32_t)v, pk.c1, pk.c2, pk.c3, pk.k0, pk.k1, rr);
                 e = -__logf(u01_open(rr[0]));
             }
             val = pv / e;
@@ -722,26 +784,45 @@ __global__ __launch_bounds__(256) void topk_token_kernel(const SmPartA* __restri
 size_t sample_ws_bytes(int rows) {
     return (size_t)rows * QS_TK_KEYS * 4 + (size_t)rows * sizeof(TkRow) + (size_t)rows * QS_SM_CHUNKS * sizeof(SmPartA);
 }
-int sample_top_k_top_p(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
-                       const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
-                       int64_t* token, int64_t token_stride, int T, int V, void* ws, hipStream_t st) {
+static bool g_tk_hist_attr = false;   // topk_hist_kernel's LDS attribute is set (shared by both instantiations)
+template <bool SEEDED>
+static int sample_top_k_top_p_impl(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
+                                   const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
+                                   int64_t* token, int64_t token_stride, int T, int V, SeedRows sr, void* ws, hipStream_t st) {
     if (T == 0) return 0;
     uint32_t* hist = reinterpret_cast<uint32_t*>(ws);
     TkRow* rows = reinterpret_cast<TkRow*>(reinterpret_cast<char*>(ws) + (size_t)T * QS_TK_KEYS * 4);
     SmPartA* part_a = reinterpret_cast<SmPartA*>(reinterpret_cast<char*>(rows) + (size_t)T * sizeof(TkRow));
-    static bool hist_attr = false;
-    if (!hist_attr) {
+    if (!g_tk_hist_attr) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(topk_hist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 QS_TK_KEYS * 2) != hipSuccess)
             return -8;
-        hist_attr = true;
+        g_tk_hist_attr = true;
     }
     hipLaunchKernelGGL(topk_hist_kernel, dim3((V + QS_TK_HCHUNK - 1) / QS_TK_HCHUNK, T), dim3(1024), QS_TK_KEYS * 2, st, logits, hist, V);
     hipLaunchKernelGGL(topk_select_kernel, dim3(T), dim3(1024), 0, st, hist, temperature, top_k, top_p, rows, V);
-    hipLaunchKernelGGL(topk_write_kernel, dim3(QS_SM_CHUNKS, T), dim3(256), 0, st, logits, rows, exponential, seed, offset,
-                       rng_state, probs, part_a, V);
+    hipLaunchKernelGGL(topk_write_kernel<SEEDED>, dim3(QS_SM_CHUNKS, T), dim3(256), 0, st, logits, rows, exponential, seed, offset,
+                       rng_state, probs, part_a, V, sr);
     hipLaunchKernelGGL(topk_token_kernel, dim3(1), dim3(256), 0, st, part_a, token, token_stride, rng_state, T);
     return 0;
+}
+int sample_top_k_top_p(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
+                       const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
+                       int64_t* token, int64_t token_stride, int T, int V, void* ws, hipStream_t st) {
+    return sample_top_k_top_p_impl<false>(logits, temperature, top_k, top_p, exponential, seed, offset, rng_state, probs, token,
+                                          token_stride, T, V, SeedRows{}, ws, st);
+}
+int sample_top_k_top_p_seeded(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
+                              const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
+                              int64_t* token, int64_t token_stride, int T, int V, const int64_t* seq_seeds,
+                              const int32_t* seq_seeded, const int32_t* base_pos, int nseq, int rows_per_seq, int j_base,
+                              int draw_stream, void* ws, hipStream_t st) {
+    if (!seq_seeds || !seq_seeded || !base_pos || rows_per_seq < 1 || (int64_t)nseq * rows_per_seq < T || j_base < 0 ||
+        j_base + rows_per_seq > 65536 || draw_stream < 1 || draw_stream > 0x7FFF)
+        return -1;
+    const SeedRows sr{seq_seeds, seq_seeded, base_pos, rows_per_seq, j_base, (uint32_t)draw_stream};
+    return sample_top_k_top_p_impl<true>(logits, temperature, top_k, top_p, exponential, seed, offset, rng_state, probs, token,
+                                         token_stride, T, V, sr, ws, st);
 }
 
 // advance_step_flashattn_kernel without the CUDA-graph padding branch (num_seqs == num_queries).

@@ -681,22 +681,43 @@ def lm_head_softmax_argmax(hidden, lm_head, logits, probs, token):
           _head_ws[key].data_ptr(), _stream())
 
 
+def _seq_seed_args(seq_seeds, seq_seeded, base_pos, nseq: int):
+    """The per-sequence arrays of the seeded entries: all three or none."""
+    given = [t is not None for t in (seq_seeds, seq_seeded, base_pos)]
+    if not any(given):
+        return None
+    if not all(given):
+        raise RuntimeError("seq_seeds, seq_seeded and base_pos go together")
+    for t, name in ((seq_seeds, "seq_seeds"), (seq_seeded, "seq_seeded"), (base_pos, "base_pos")):
+        if t.numel() < nseq:
+            raise RuntimeError(f"{name} has {t.numel()} entries, {nseq} sequences need one each")
+    return (_chk(seq_seeds, "seq_seeds", _I64), _chk(seq_seeded, "seq_seeded", _I32), _chk(base_pos, "base_pos", _I32))
+
+
 def rejection_sample(target_with_bonus_probs, bonus_token_ids, draft_probs, draft_token_ids, out_tokens, accepted,
                      recovered, counters=None, uniform=None, exponential=None, seed: int = 0, offset: int = 0,
-                     rng_state=None, workspace=None, active_lens=None):
+                     rng_state=None, workspace=None, active_lens=None, seq_seeds=None, seq_seeded=None, base_pos=None):
+    """seq_seeds [B] int64 / seq_seeded [B] int32 / base_pos [B] int32 (all or none): rows b with seq_seeded[b] != 0 draw
+    from Philox keyed by (seq_seeds[b], base_pos[b]) alone -- qspec_rejection_sample_seeded (include/qspec_hip.h)."""
     B, k, V = draft_probs.shape
     # draft_probs / draft_token_ids / bonus_token_ids may be strided views (step-major draft buffers)
     if draft_probs.stride(2) != 1 or draft_probs.dtype != _F32 or draft_token_ids.dtype != _I64 \
             or bonus_token_ids.dtype != _I64 or not draft_probs.is_cuda:
         raise RuntimeError("draft_probs must be fp32 with unit inner stride; ids int64; all on the GPU")
-    _call("qspec_rejection_sample", _chk(target_with_bonus_probs, "target_with_bonus_probs", _F32),
-          bonus_token_ids.data_ptr(), draft_probs.data_ptr(), draft_token_ids.data_ptr(),
-          _opt(uniform, "uniform", _F32), _opt(exponential, "exponential", _F32), seed, offset,
-          _opt(rng_state, "rng_state", _I64), B, k, V, draft_probs.stride(0), draft_probs.stride(1),
-          draft_token_ids.stride(0), draft_token_ids.stride(1),
-          bonus_token_ids.stride(0) if bonus_token_ids.numel() > 1 else 1, _chk(out_tokens, "out_tokens", _I64),
-          _chk(accepted, "accepted", _U8), _chk(recovered, "recovered", _I64), _opt(counters, "counters", _I64),
-          _opt(active_lens, "active_lens", _I32), _sampler_ws(B * k, draft_probs.device, workspace).data_ptr(), _stream())
+    seeded = _seq_seed_args(seq_seeds, seq_seeded, base_pos, B)
+    args = (_chk(target_with_bonus_probs, "target_with_bonus_probs", _F32),
+            bonus_token_ids.data_ptr(), draft_probs.data_ptr(), draft_token_ids.data_ptr(),
+            _opt(uniform, "uniform", _F32), _opt(exponential, "exponential", _F32), seed, offset,
+            _opt(rng_state, "rng_state", _I64), B, k, V, draft_probs.stride(0), draft_probs.stride(1),
+            draft_token_ids.stride(0), draft_token_ids.stride(1),
+            bonus_token_ids.stride(0) if bonus_token_ids.numel() > 1 else 1, _chk(out_tokens, "out_tokens", _I64),
+            _chk(accepted, "accepted", _U8), _chk(recovered, "recovered", _I64), _opt(counters, "counters", _I64),
+            _opt(active_lens, "active_lens", _I32))
+    ws = _sampler_ws(B * k, draft_probs.device, workspace).data_ptr()
+    if seeded is None:
+        _call("qspec_rejection_sample", *args, ws, _stream())
+    else:
+        _call("qspec_rejection_sample_seeded", *args, *seeded, ws, _stream())
 
 
 _sample_ws = {}
@@ -710,16 +731,33 @@ def sample_workspace(rows: int, device):
     return _sample_ws[key]
 
 
+def new_sample_workspace(rows: int, device):
+    """A private zero-filled histogram workspace of sample_top_k_top_p for `rows` rows (callers that must not rely on the
+    lazily created shared one being zeroed outside a graph capture)."""
+    return torch.zeros(int(_lib.load().qspec_sample_workspace_bytes(rows)), dtype=torch.uint8, device=device)
+
+
 def sample_top_k_top_p(logits, probs, token, temperature=None, top_k=None, top_p=None, exponential=None, seed: int = 0,
-                       offset: int = 0, rng_state=None, workspace=None):
+                       offset: int = 0, rng_state=None, workspace=None, seq_seeds=None, seq_seeded=None, base_pos=None,
+                       rows_per_seq: int = 1, j_base: int = 0, draw_stream: int = 2):
     """Sampler.forward for non-greedy rows (sampler.py:216-316): temperature, top-k / top-p masking, softmax, multinomial by
-    exponential noise.  temperature / top_p [T] fp32, top_k [T] int32 on the device (None: 1.0 / off)."""
+    exponential noise.  temperature / top_p [T] fp32, top_k [T] int32 on the device (None: 1.0 / off).
+    seq_seeds int64 / seq_seeded int32 / base_pos int32, one entry per SEQUENCE (all or none): row t belongs to sequence
+    t // rows_per_seq, and rows of seeded sequences draw from Philox keyed by (seed, base_pos, draw_stream,
+    j_base + t % rows_per_seq) alone -- qspec_sample_top_k_top_p_seeded (include/qspec_hip.h)."""
     T, V = logits.shape
     ws = workspace if workspace is not None else sample_workspace(T, logits.device)
-    _call("qspec_sample_top_k_top_p", _chk(logits, "logits", _F16), _opt(temperature, "temperature", _F32),
-          _opt(top_k, "top_k", _I32), _opt(top_p, "top_p", _F32), _opt(exponential, "exponential", _F32), seed, offset,
-          _opt(rng_state, "rng_state", _I64), _chk(probs, "probs", _F32), token.data_ptr(), token.stride(0) if token.dim() else 1,
-          T, V, ws.data_ptr(), _stream())
+    nseq = (T + rows_per_seq - 1) // max(1, rows_per_seq)
+    seeded = _seq_seed_args(seq_seeds, seq_seeded, base_pos, nseq)
+    args = (_chk(logits, "logits", _F16), _opt(temperature, "temperature", _F32),
+            _opt(top_k, "top_k", _I32), _opt(top_p, "top_p", _F32), _opt(exponential, "exponential", _F32), seed, offset,
+            _opt(rng_state, "rng_state", _I64), _chk(probs, "probs", _F32), token.data_ptr(), token.stride(0) if token.dim() else 1,
+            T, V)
+    if seeded is None:
+        _call("qspec_sample_top_k_top_p", *args, ws.data_ptr(), _stream())
+    else:
+        _call("qspec_sample_top_k_top_p_seeded", *args, *seeded, seq_seeds.numel(), rows_per_seq, j_base, draw_stream,
+              ws.data_ptr(), _stream())
 
 
 def typical_acceptance_sample(target_with_bonus_probs, bonus_token_ids, draft_token_ids, posterior_threshold: float,

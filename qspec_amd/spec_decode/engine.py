@@ -156,6 +156,16 @@ class QSpecEngine:
         self.v_samp_topk = torch.full((T,), -1, dtype=torch.int32, device=dev)
         self.v_samp_topp = torch.ones(T, dtype=torch.float32, device=dev)
         self._samp_host = [(0.0, -1, 1.0)] * B
+        # per-request seeds (SamplingParams.seed): a seeded sampled request draws from Philox keyed by (seed, seq_lens at the
+        # start of the cycle, stream, j, v) alone -- the same tokens whatever slot it holds and whoever shares the batch
+        # (include/qspec_hip.h, "seeded draws").  seq_seeded[b] == 0: the engine stream (rng_state), as before
+        self.seq_seed = torch.zeros(B, dtype=i64, device=dev)
+        self.seq_seeded = torch.zeros(B, dtype=i32, device=dev)
+        self._seed_host: List[Optional[int]] = [None] * B
+        # the sampling front end's histogram workspaces (draft / non-speculative rows, verify rows), zero-filled here --
+        # outside any capture -- and left zeroed by every call
+        self._sample_ws_d = ops.new_sample_workspace(B, dev)
+        self._sample_ws_v = ops.new_sample_workspace(T, dev)
         self._mode_sampling = False
         self._graph_s: Optional[torch.cuda.CUDAGraph] = None       # the cycle with the sampling front end
         self._graph_draft_s: Optional[torch.cuda.CUDAGraph] = None
@@ -232,7 +242,7 @@ class QSpecEngine:
         logits = self.model.compute_logits(hs[last].contiguous(), s)
         probs = torch.empty(n, cfg.vocab_size, dtype=torch.float32, device=dev)
         tok = torch.empty(n, dtype=torch.int64, device=dev)
-        self._first_token(logits, probs, tok, list(slots))
+        self._first_token(logits, probs, tok, list(slots), lens)
         for i, (b, T) in enumerate(zip(slots, lens)):
             self.seq_lens[b] = T + 1
             self.last_token[b] = tok[i]
@@ -273,7 +283,7 @@ class QSpecEngine:
         logits = self.model.compute_logits(hs[T - 1:T], s)
         probs = torch.empty(1, cfg.vocab_size, dtype=torch.float32, device=dev)
         tok = torch.empty(1, dtype=torch.int64, device=dev)
-        self._first_token(logits, probs, tok, [b])
+        self._first_token(logits, probs, tok, [b], [T])
         self.seq_lens[b] = T + 1
         self.last_token[b] = tok[0]
         self.gen_tokens[b].fill_(-1)
@@ -285,14 +295,18 @@ class QSpecEngine:
         if sync:
             torch.cuda.synchronize()
 
-    def _first_token(self, logits, probs, tok, slots: List[int]) -> None:
-        """The target's first token of freshly admitted prompts: greedy, or sampled with the slots' parameters."""
+    def _first_token(self, logits, probs, tok, slots: List[int], prompt_lens: List[int]) -> None:
+        """The target's first token of freshly admitted prompts: greedy, or sampled with the slots' parameters (a seeded
+        request: target stream, j = 0, base position = its prompt length)."""
         if all(self._samp_host[b][0] < 1e-5 for b in slots):
             ops.softmax_argmax(logits, probs, tok)
             return
         idx = torch.tensor(slots, dtype=torch.int64, device=self.device)
         ops.sample_top_k_top_p(logits, probs, tok, self.samp_temp[idx].contiguous(), self.samp_topk[idx].contiguous(),
-                               self.samp_topp[idx].contiguous(), rng_state=self.sampler.rng_state)
+                               self.samp_topp[idx].contiguous(), rng_state=self.sampler.rng_state,
+                               seq_seeds=self.seq_seed[idx].contiguous(), seq_seeded=self.seq_seeded[idx].contiguous(),
+                               base_pos=torch.tensor(prompt_lens, dtype=torch.int32, device=self.device),
+                               rows_per_seq=1, j_base=0, draw_stream=2)
 
     def free_slot(self, slot: int) -> None:
         """The request in `slot` has finished (EOS / max_tokens / aborted): the slot goes back to empty."""
@@ -300,7 +314,7 @@ class QSpecEngine:
         self.gen_lens[slot] = 0
         self._len_ub[slot] = 0
         self._gen_ub[slot] = 0
-        self.set_sampling_params(slot)          # back to greedy
+        self.set_sampling_params(slot)          # back to greedy, no seed
         if self._bt_host[slot] is not None:
             # the request's blocks go back to the scheduler: the slot must not keep a table (and a capacity) that the
             # next admission could pass validation against.  Contiguous mode: the slot's own default range again;
@@ -315,11 +329,19 @@ class QSpecEngine:
             self._bt_host[slot] = None
         self.n_active = sum(1 for v in self._len_ub if v > 0)
 
-    def set_sampling_params(self, slot: int, temperature: float = 0.0, top_k: int = -1, top_p: float = 1.0) -> None:
+    def set_sampling_params(self, slot: int, temperature: float = 0.0, top_k: int = -1, top_p: float = 1.0,
+                            seed: Optional[int] = None) -> None:
         """The request in `slot` samples with these parameters (vllm/sampling_params.py; temperature < 1e-5 = greedy, for
-        which vLLM itself resets top_k / top_p).  Uploaded only when they change."""
+        which vLLM itself resets top_k / top_p).  seed (SamplingParams.seed, taken mod 2^64): the request's draws depend
+        on it and its own positions only; a greedy request makes no draws and ignores it.  Uploaded only when they
+        change; a change never re-captures the graph (the kernels read the seed arrays at replay)."""
         if temperature < 1e-5:
-            temperature, top_k, top_p = 0.0, -1, 1.0
+            temperature, top_k, top_p, seed = 0.0, -1, 1.0, None
+        want_seed = None if seed is None else int(seed) % (1 << 64)
+        if self._seed_host[slot] != want_seed:
+            self.seq_seed[slot] = 0 if want_seed is None else want_seed - (1 << 64) * (want_seed >= 1 << 63)
+            self.seq_seeded[slot] = 0 if want_seed is None else 1
+            self._seed_host[slot] = want_seed
         want = (float(temperature), int(top_k) if top_k and top_k > 0 else -1, float(top_p))
         if self._samp_host[slot] == want:
             return
@@ -438,7 +460,8 @@ class QSpecEngine:
                            embedded=emb_d is not None)
             if self._mode_sampling:   # draft tokens are SAMPLED from the processed draft distribution (sampler.py:216-316)
                 m.sample(hs, self.scratch_draft, self.draft_probs_kbv[i], self.draft_ids_kb[i], self.samp_temp, self.samp_topk,
-                         self.samp_topp, self.sampler.rng_state, shard_vocab=draft_sv)
+                         self.samp_topp, self.sampler.rng_state, shard_vocab=draft_sv, workspace=self._sample_ws_d,
+                         **self._seed_args(rows_per_seq=1, j_base=i, draw_stream=1))
             else:
                 m.sample_greedy(hs, self.scratch_draft, self.draft_probs_kbv[i], self.draft_ids_kb[i], shard_vocab=draft_sv)
             if i != k - 1:  # _gpu_advance_step (draft_model_runner.py:78-135)
@@ -456,19 +479,27 @@ class QSpecEngine:
         hs = m.forward(self.v_tokens, self.v_pos, self.kv_caches, self.md_verify, self.scratch_verify, w4a4=False,
                        embedded=emb_v is not None)
         hook = self._verify_logits_hook(draft_ids)
+        seeded = {}
         if self._mode_sampling:
             m.sample(hs, self.scratch_verify, self.target_probs.view(B * (k + 1), -1), self.target_tokens.view(-1),
                      self.v_samp_temp, self.v_samp_topk, self.v_samp_topp, self.sampler.rng_state, shard_vocab=True,
-                     logits_hook=hook)
+                     logits_hook=hook, workspace=self._sample_ws_v,
+                     **self._seed_args(rows_per_seq=k + 1, j_base=0, draw_stream=2))
+            seeded = self._seed_args()
         else:
             m.sample_greedy(hs, self.scratch_verify, self.target_probs.view(B * (k + 1), -1), self.target_tokens.view(-1),
                             shard_vocab=True, logits_hook=hook)
         # _verify_tokens (:861-970): bonus = the target's own token at the last position
         self.sampler.forward(self.target_probs, self.target_tokens[:, k], draft_probs, draft_ids, out=self.out_tokens,
                              accepted=self.accepted, recovered=self.recovered, uniform=self.inject_uniform,
-                             exponential=self.inject_exponential, active_lens=self.eff_lens)
+                             exponential=self.inject_exponential, active_lens=self.eff_lens, **seeded)
         # _create_output_sampler_list bookkeeping (:972-1063)
         ops.spec_commit(self.out_tokens, self.seq_lens, self.last_token, self.gen_tokens, self.gen_lens)
+
+    def _seed_args(self, **rows) -> dict:
+        """The per-sequence seed arguments of the sampling calls: base position = seq_lens at the start of the cycle
+        (read on the device at replay, restored by recover(), so a replayed cycle repeats its draws)."""
+        return dict(seq_seeds=self.seq_seed, seq_seeded=self.seq_seeded, base_pos=self.seq_lens, **rows)
 
     @torch.no_grad()
     def _verify_logits_hook(self, draft_ids):
@@ -498,7 +529,12 @@ class QSpecEngine:
                                self.d_slots, self.d_ctx)                   # [last token] at position seq_len - 1
         hs = m.forward(self.d_tokens, self.d_pos, self.kv_caches, self.md_draft, self.scratch_draft, w4a4=False)
         logits = m.compute_logits(hs, self.scratch_draft)
-        ops.softmax_argmax(logits, self.draft_probs_kbv[0], self.draft_ids_kb[0])
+        if self._sampling_on():   # sampled requests sample (a seeded one: target stream, j = 0); greedy rows take the argmax
+            ops.sample_top_k_top_p(logits, self.draft_probs_kbv[0], self.draft_ids_kb[0], self.samp_temp, self.samp_topk,
+                                   self.samp_topp, rng_state=self.sampler.rng_state, workspace=self._sample_ws_d,
+                                   **self._seed_args(rows_per_seq=1, j_base=0, draw_stream=2))
+        else:
+            ops.softmax_argmax(logits, self.draft_probs_kbv[0], self.draft_ids_kb[0])
         self.out_tokens.fill_(-1)
         self.out_tokens[:, 0] = torch.where(self.eff_lens > 0, self.draft_ids_kb[0], torch.full_like(self.draft_ids_kb[0], -1))
         ops.spec_commit(self.out_tokens, self.seq_lens, self.last_token, self.gen_tokens, self.gen_lens)

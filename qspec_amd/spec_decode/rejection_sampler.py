@@ -58,11 +58,14 @@ class RejectionSampler:
                 seeded_seqs: Optional[Dict[int, torch.Generator]] = None, *, out: Optional[torch.Tensor] = None,
                 accepted: Optional[torch.Tensor] = None, recovered: Optional[torch.Tensor] = None,
                 uniform: Optional[torch.Tensor] = None, exponential: Optional[torch.Tensor] = None,
-                active_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+                active_lens: Optional[torch.Tensor] = None, seq_seeds: Optional[torch.Tensor] = None,
+                seq_seeded: Optional[torch.Tensor] = None, base_pos: Optional[torch.Tensor] = None) -> torch.Tensor:
         """-> output_token_ids [B, k+1] (int64; -1 = no token).
         seeded_seqs {row: torch.Generator} (rejection_sampler.py:60-67,229-250,387-399): those rows draw their
         uniforms and exponentials from their own generator, the others from the default stream -- done with torch on
         the slow (eager) path and handed to the kernels as injected draws.
+        seq_seeds [B] int64 / seq_seeded [B] int32 / base_pos [B] int32 (engine; all or none): the same on the device --
+        rows with seq_seeded != 0 draw from Philox keyed by (seed, base position) alone, inside a captured graph.
         active_lens [B] int32 (engine): rows with active_lens <= 0 are empty batch slots -- no output, not counted."""
         B, k, V = draft_probs.shape
         dev = draft_probs.device
@@ -84,7 +87,8 @@ class RejectionSampler:
         bonus = bonus_token_ids.squeeze(-1) if bonus_token_ids.dim() == 2 else bonus_token_ids  # a view, never a copy
         ops.rejection_sample(target_with_bonus_probs, bonus, draft_probs, draft_token_ids, out,
                              accepted, recovered, self.counters, uniform=uniform, exponential=exponential,
-                             rng_state=self.rng_state, active_lens=active_lens)
+                             rng_state=self.rng_state, active_lens=active_lens, seq_seeds=seq_seeds,
+                             seq_seeded=seq_seeded, base_pos=base_pos)
         return out
 
     __call__ = forward

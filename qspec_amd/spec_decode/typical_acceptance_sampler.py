@@ -29,9 +29,11 @@ class TypicalAcceptanceSampler(RejectionSampler):
                 draft_probs: Optional[torch.Tensor], draft_token_ids: torch.Tensor, seeded_seqs=None, *,
                 out: Optional[torch.Tensor] = None, accepted: Optional[torch.Tensor] = None,
                 recovered: Optional[torch.Tensor] = None, uniform=None, exponential=None,
-                active_lens: Optional[torch.Tensor] = None) -> torch.Tensor:
+                active_lens: Optional[torch.Tensor] = None, seq_seeds=None, seq_seeded=None,
+                base_pos=None) -> torch.Tensor:
         """-> output_token_ids [B, k+1] (int64; -1 = no token).  draft_probs is unused (typical_acceptance_sampler.py:62);
-        seeded_seqs / uniform / exponential are accepted for call compatibility with the rejection sampler and ignored."""
+        seeded_seqs / uniform / exponential / seq_seeds / seq_seeded / base_pos are accepted for call compatibility with the
+        rejection sampler and ignored (no random draws)."""
         B, k1, V = target_with_bonus_probs.shape
         k = k1 - 1
         dev = target_with_bonus_probs.device

@@ -551,8 +551,10 @@ class SpecDecodeWorker:
             toks.append(data.get_token_ids())
             tables.append(s.block_tables.get(seq_id) if s.block_tables else None)
             sp = s.sampling_params   # before the prompt pass: the first token is sampled with them too
+            seed = getattr(sp, "seed", None)   # (forwarded only when set: an engine double need not know the keyword)
             self.engine.set_sampling_params(b, getattr(sp, "temperature", 0.0) or 0.0, getattr(sp, "top_k", -1) or -1,
-                                            getattr(sp, "top_p", 1.0) if sp is not None else 1.0)
+                                            getattr(sp, "top_p", 1.0) if sp is not None else 1.0,
+                                            **({} if seed is None else {"seed": seed}))
         try:
             self.engine.add_sequences_to(slots, toks, tables)
         except Exception:
