@@ -443,6 +443,58 @@ int qspec_rejection_sample_seeded(const float* target_with_bonus_probs, const in
                                   const int32_t* active_lens, const int64_t* seq_seeds, const int32_t* seq_seeded,
                                   const int32_t* base_pos, void* workspace, void* stream);
 
+/* Logit processors: the rest of Sampler.forward's pipeline (vllm/model_executor/layers/sampler.py:258-278) inside the captured
+ *   cycle: _apply_min_tokens_penalty (:338-384), apply_penalties (vllm/model_executor/layers/utils.py:24-57) and _apply_min_p
+ *   (:416-430).  Under speculative decoding EVERY row is processed exactly as the non-speculative sampler would process that
+ *   position given the same prefix: row j of a sequence (draft step j, 0-based, or verify row j = 0..k) sees the request's
+ *   prompt tokens, the outputs committed before the cycle plus the in-flight draft tokens d_1 .. d_j, and a generated length of
+ *   committed + j.  (The reference's own MQA path hands the sampler one token list per sequence for k+1 rows per sequence,
+ *   mqa_scorer.py:34-47 / sampling_metadata.py:467-471, and has no usable behaviour here.)
+ *   tok_table [num_slots, vocab] uint32: bit 31 = the token occurs in the prompt, low 31 bits = its count in the outputs.
+ *   counted_len [num_slots] int32: how many of gen_tokens[slot][0 .. gen_lens[slot]) are counted.
+ *   qspec_logit_table_set_prompt (admission, outside the graph): clears the slot's row, marks prompt_ids, counts output_ids
+ *     (the outputs a re-admitted request already had), counted_len[slot] = 0.  Ids outside [0, vocab) are ignored.
+ *   qspec_logit_table_catch_up (head of a cycle): for every slot with need_counts != 0 adds
+ *     gen_tokens[slot][counted_len .. gen_lens) and sets counted_len = gen_lens.  Driven by gen_lens alone, hence idempotent:
+ *     a cycle re-run from qspec_spec_snapshot(restore) finds counted_len == gen_lens and adds nothing.
+ *   qspec_process_logits: out [tokens, vocab] = processed logits, OUT OF PLACE (logits stay readable).  Row t belongs to
+ *     sequence t / rows_per_seq (slot slot_ids[sequence], or the sequence index itself when slot_ids is NULL) with
+ *     j = j_base + t % rows_per_seq.  Per element, in the reference's order and with its fp16 roundings:
+ *       stop ids -> -inf while gen_base + gen_lens + j < min_tokens;
+ *       x = x > 0 ? x / rep : x * rep where the token is in the prompt or the outputs (in-flight ones included);
+ *       x -= freq * fp16(count);  x -= pres * (count > 0).
+ *     repetition / frequency / presence [num_slots] fp16 (the reference keeps them in the logits' dtype), min_tokens / gen_base /
+ *     gen_lens / num_stop_ids [num_slots] int32, stop_ids [num_slots, stop_ids_per_slot] int32 (<= QS_MAX_STOP_IDS), all
+ *     read when the call runs: changing a request's parameters never re-captures a graph.  draft_ids: in-flight token i
+ *     (0-based) of slot b at b*ids_stride_b + i*ids_stride_k, draft_rows of them per slot; j_base + rows_per_seq - 1 <=
+ *     draft_rows.  Rows of slots with active_lens <= 0 (may be NULL) are copied through; neutral parameters give back the
+ *     input bits.
+ *   qspec_sample_top_k_top_p_min_p(_seeded): qspec_sample_top_k_top_p(_seeded) with min_p [tokens] fp32 (NULL: none, the same
+ *     bits as the entry without it): tokens with exp(l - max) < min_p are masked behind top-k / top-p, no launch added; greedy
+ *     rows ignore it (sampling_params.py:344). */
+#define QS_MAX_STOP_IDS 16
+int qspec_logit_table_set_prompt(uint32_t* tok_table, int32_t* counted_len, int num_slots, int vocab, int slot,
+                                 const int64_t* prompt_ids, int num_prompt, const int64_t* output_ids, int num_outputs,
+                                 void* stream);
+int qspec_logit_table_catch_up(uint32_t* tok_table, int32_t* counted_len, const int32_t* need_counts, int num_slots, int vocab,
+                               const int64_t* gen_tokens, int gen_cap, const int32_t* gen_lens, void* stream);
+int qspec_process_logits(const qspec_half* logits, qspec_half* out, int tokens, int vocab, const uint32_t* tok_table,
+                         int num_slots, const int32_t* slot_ids, const int32_t* active_lens, const qspec_half* repetition,
+                         const qspec_half* frequency, const qspec_half* presence, const int32_t* min_tokens,
+                         const int32_t* gen_base, const int32_t* gen_lens, const int32_t* stop_ids, const int32_t* num_stop_ids,
+                         int stop_ids_per_slot, const int64_t* draft_ids, int draft_rows, int64_t ids_stride_b,
+                         int64_t ids_stride_k, int rows_per_seq, int j_base, void* stream);
+int qspec_sample_top_k_top_p_min_p(const qspec_half* logits, const float* temperature, const int32_t* top_k, const float* top_p,
+                                   const float* min_p, const float* exponential, uint64_t seed, uint64_t offset,
+                                   uint64_t* rng_state, float* probs, int64_t* token, int64_t token_stride, int tokens, int vocab,
+                                   void* workspace, void* stream);
+int qspec_sample_top_k_top_p_min_p_seeded(const qspec_half* logits, const float* temperature, const int32_t* top_k,
+                                          const float* top_p, const float* min_p, const float* exponential, uint64_t seed,
+                                          uint64_t offset, uint64_t* rng_state, float* probs, int64_t* token,
+                                          int64_t token_stride, int tokens, int vocab, const int64_t* seq_seeds,
+                                          const int32_t* seq_seeded, const int32_t* base_pos, int num_seqs, int rows_per_seq,
+                                          int j_base, int draw_stream, void* workspace, void* stream);
+
 /* TypicalAcceptanceSampler.forward(target_with_bonus_probs, bonus_token_ids, draft_probs, draft_token_ids)
  *   vllm/model_executor/layers/typical_acceptance_sampler.py:37-172 (MEDUSA 3.3.1), selected by
  *   draft_token_acceptance_method = "typical_acceptance_sampler" (vllm/spec_decode/spec_decode_worker.py:95-110).

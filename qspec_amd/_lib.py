@@ -96,6 +96,13 @@ SIGNATURES = {
                                              _i, _i, _i, _i, _vp, _vp]),
     "qspec_rejection_sample_seeded": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _i, _i, _i, _i64, _i64, _i64, _i64,
                                            _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qspec_sample_top_k_top_p_min_p": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "qspec_sample_top_k_top_p_min_p_seeded": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp,
+                                                   _vp, _i, _i, _i, _i, _vp, _vp]),
+    "qspec_logit_table_set_prompt": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "qspec_logit_table_catch_up": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "qspec_process_logits": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i64,
+                                  _i64, _i, _i, _vp]),
     "qspec_typical_acceptance_sample": (_i, [_vp, _vp, _vp, _f, _f, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qspec_advance_step_flashattn": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "qspec_spec_prepare_draft": (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),

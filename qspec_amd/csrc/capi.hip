@@ -518,6 +518,100 @@ int qspec_sample_top_k_top_p_seeded(const qspec_half* logits, const float* tempe
                                                        seq_seeded, base_pos, num_seqs, rows_per_seq, j_base, draw_stream,
                                                        workspace, ST));
 }
+// min_p twins of qspec_sample_top_k_top_p(_seeded): _apply_min_p (vllm/model_executor/layers/sampler.py:416-430) as one more
+// boundary of the selection kernel; min_p NULL = the entry without it, bit for bit.
+int qspec_sample_top_k_top_p_min_p(const qspec_half* logits, const float* temperature, const int32_t* top_k, const float* top_p,
+                                   const float* min_p, const float* exponential, uint64_t seed, uint64_t offset,
+                                   uint64_t* rng_state, float* probs, int64_t* token, int64_t token_stride, int tokens, int vocab,
+                                   void* workspace, void* stream) {
+    const char* op = "qspec_sample_top_k_top_p_min_p";
+    if (tokens < 0) return fail("%s: tokens < 0", op);
+    if (tokens == 0) return 0;
+    NONNULL(op, logits); NONNULL(op, probs); NONNULL(op, token); NONNULL(op, workspace);
+    if (vocab < 1) return fail("%s: vocab < 1", op);
+    return finish(op, qspec::sample_top_k_top_p_min_p(CH(logits), temperature, top_k, top_p, min_p, exponential, seed, offset,
+                                                      rng_state, probs, token, token_stride, tokens, vocab, workspace, ST));
+}
+int qspec_sample_top_k_top_p_min_p_seeded(const qspec_half* logits, const float* temperature, const int32_t* top_k,
+                                          const float* top_p, const float* min_p, const float* exponential, uint64_t seed,
+                                          uint64_t offset, uint64_t* rng_state, float* probs, int64_t* token,
+                                          int64_t token_stride, int tokens, int vocab, const int64_t* seq_seeds,
+                                          const int32_t* seq_seeded, const int32_t* base_pos, int num_seqs, int rows_per_seq,
+                                          int j_base, int draw_stream, void* workspace, void* stream) {
+    const char* op = "qspec_sample_top_k_top_p_min_p_seeded";
+    if (tokens < 0) return fail("%s: tokens < 0", op);
+    if (tokens == 0) return 0;
+    NONNULL(op, logits); NONNULL(op, probs); NONNULL(op, token); NONNULL(op, workspace);
+    NONNULL(op, seq_seeds); NONNULL(op, seq_seeded); NONNULL(op, base_pos);
+    if (vocab < 1) return fail("%s: vocab < 1", op);
+    if (rows_per_seq < 1) return fail("%s: rows_per_seq=%d must be >= 1", op, rows_per_seq);
+    if ((int64_t)num_seqs * rows_per_seq < tokens)
+        return fail("%s: num_seqs=%d x rows_per_seq=%d does not cover tokens=%d", op, num_seqs, rows_per_seq, tokens);
+    if (j_base < 0 || j_base + rows_per_seq > 65536)
+        return fail("%s: j_base=%d + rows_per_seq=%d outside the 16-bit sub-index", op, j_base, rows_per_seq);
+    if (draw_stream != 1 && draw_stream != 2) return fail("%s: draw_stream=%d must be 1 (draft) or 2 (target)", op, draw_stream);
+    return finish(op, qspec::sample_top_k_top_p_min_p_seeded(CH(logits), temperature, top_k, top_p, min_p, exponential, seed,
+                                                             offset, rng_state, probs, token, token_stride, tokens, vocab,
+                                                             seq_seeds, seq_seeded, base_pos, num_seqs, rows_per_seq, j_base,
+                                                             draw_stream, workspace, ST));
+}
+// Logit processors: Sampler.forward's _apply_min_tokens_penalty + apply_penalties (vllm/model_executor/layers/sampler.py:258-266,
+// :338-384; vllm/model_executor/layers/utils.py:24-57), per row of a speculative cycle (include/qspec_hip.h, "logit processors").
+int qspec_logit_table_set_prompt(uint32_t* tok_table, int32_t* counted_len, int num_slots, int vocab, int slot,
+                                 const int64_t* prompt_ids, int num_prompt, const int64_t* output_ids, int num_outputs,
+                                 void* stream) {
+    const char* op = "qspec_logit_table_set_prompt";
+    NONNULL(op, tok_table); NONNULL(op, counted_len);
+    if (vocab < 1) return fail("%s: vocab < 1", op);
+    if (slot < 0 || slot >= num_slots) return fail("%s: slot=%d outside the %d slots of the table", op, slot, num_slots);
+    if (num_prompt < 0 || num_outputs < 0) return fail("%s: negative token count", op);
+    if (num_prompt > 0) NONNULL(op, prompt_ids);
+    if (num_outputs > 0) NONNULL(op, output_ids);
+    return finish(op, qspec::logit_table_set_prompt(tok_table, vocab, slot, prompt_ids, num_prompt, output_ids, num_outputs,
+                                                    counted_len, ST));
+}
+int qspec_logit_table_catch_up(uint32_t* tok_table, int32_t* counted_len, const int32_t* need_counts, int num_slots, int vocab,
+                               const int64_t* gen_tokens, int gen_cap, const int32_t* gen_lens, void* stream) {
+    const char* op = "qspec_logit_table_catch_up";
+    if (num_slots < 0) return fail("%s: num_slots < 0", op);
+    if (num_slots == 0) return 0;
+    NONNULL(op, tok_table); NONNULL(op, counted_len); NONNULL(op, need_counts); NONNULL(op, gen_tokens); NONNULL(op, gen_lens);
+    if (vocab < 1) return fail("%s: vocab < 1", op);
+    if (gen_cap < 1) return fail("%s: gen_cap=%d must be >= 1", op, gen_cap);
+    return finish(op, qspec::logit_table_catch_up(num_slots, vocab, tok_table, counted_len, need_counts, gen_tokens, gen_cap,
+                                                  gen_lens, ST));
+}
+int qspec_process_logits(const qspec_half* logits, qspec_half* out, int tokens, int vocab, const uint32_t* tok_table,
+                         int num_slots, const int32_t* slot_ids, const int32_t* active_lens, const qspec_half* repetition,
+                         const qspec_half* frequency, const qspec_half* presence, const int32_t* min_tokens,
+                         const int32_t* gen_base, const int32_t* gen_lens, const int32_t* stop_ids, const int32_t* num_stop_ids,
+                         int stop_ids_per_slot, const int64_t* draft_ids, int draft_rows, int64_t ids_stride_b,
+                         int64_t ids_stride_k, int rows_per_seq, int j_base, void* stream) {
+    const char* op = "qspec_process_logits";
+    if (tokens < 0) return fail("%s: tokens < 0", op);
+    if (tokens == 0) return 0;
+    NONNULL(op, logits); NONNULL(op, out); NONNULL(op, tok_table); NONNULL(op, repetition); NONNULL(op, frequency);
+    NONNULL(op, presence); NONNULL(op, min_tokens); NONNULL(op, gen_base); NONNULL(op, gen_lens); NONNULL(op, stop_ids);
+    NONNULL(op, num_stop_ids);
+    if (logits == out) return fail("%s: the pass is out of place (logits == out)", op);
+    if (vocab < 1) return fail("%s: vocab < 1", op);
+    if (num_slots < 1) return fail("%s: num_slots=%d must be >= 1", op, num_slots);
+    if (rows_per_seq < 1) return fail("%s: rows_per_seq=%d must be >= 1", op, rows_per_seq);
+    if (j_base < 0) return fail("%s: j_base < 0", op);
+    if (stop_ids_per_slot < 0 || stop_ids_per_slot > QS_MAX_STOP_IDS)
+        return fail("%s: stop_ids_per_slot=%d outside 0..%d", op, stop_ids_per_slot, QS_MAX_STOP_IDS);
+    if (draft_rows < 0 || (draft_rows > 0 && !draft_ids)) return fail("%s: draft_rows=%d without draft_ids", op, draft_rows);
+    if (j_base + rows_per_seq - 1 > draft_rows)
+        return fail("%s: row j=%d needs %d in-flight tokens, draft_ids has %d rows", op, j_base + rows_per_seq - 1,
+                    j_base + rows_per_seq - 1, draft_rows);
+    if (j_base + rows_per_seq - 1 > 64) return fail("%s: more than 64 in-flight tokens", op);
+    if (!slot_ids && (int64_t)num_slots * rows_per_seq < tokens)
+        return fail("%s: num_slots=%d x rows_per_seq=%d does not cover tokens=%d", op, num_slots, rows_per_seq, tokens);
+    return finish(op, qspec::process_logits(CH(logits), H(out), tokens, vocab, tok_table, slot_ids, active_lens, CH(repetition),
+                                            CH(frequency), CH(presence), min_tokens, gen_base, gen_lens, stop_ids, num_stop_ids,
+                                            draft_rows > 0 ? draft_ids : nullptr, ids_stride_b, ids_stride_k, rows_per_seq,
+                                            j_base, num_slots, stop_ids_per_slot, ST));
+}
 int qspec_typical_acceptance_sample(const float* target_with_bonus_probs, const int64_t* bonus_token_ids,
                                     const int64_t* draft_token_ids, float posterior_threshold, float posterior_alpha, int batch,
                                     int k, int vocab, int64_t ids_stride_b, int64_t ids_stride_k, int64_t bonus_stride,

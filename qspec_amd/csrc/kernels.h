@@ -190,6 +190,24 @@ int sample_top_k_top_p_seeded(const f16* logits, const float* temperature, const
                               int64_t* token, int64_t token_stride, int T, int V, const int64_t* seq_seeds,
                               const int32_t* seq_seeded, const int32_t* base_pos, int nseq, int rows_per_seq, int j_base,
                               int draw_stream, void* ws, hipStream_t st);
+int sample_top_k_top_p_min_p(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
+                             const float* min_p, const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state,
+                             float* probs, int64_t* token, int64_t token_stride, int T, int V, void* ws, hipStream_t st);
+int sample_top_k_top_p_min_p_seeded(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
+                                    const float* min_p, const float* exponential, uint64_t seed, uint64_t offset,
+                                    uint64_t* rng_state, float* probs, int64_t* token, int64_t token_stride, int T, int V,
+                                    const int64_t* seq_seeds, const int32_t* seq_seeded, const int32_t* base_pos, int nseq,
+                                    int rows_per_seq, int j_base, int draw_stream, void* ws, hipStream_t st);
+// logit processors (min_tokens, repetition / frequency / presence penalties) and the per-slot token table they read
+int logit_table_set_prompt(uint32_t* table, int V, int slot, const int64_t* prompt, int n_prompt, const int64_t* outputs,
+                           int n_out, int32_t* counted_len, hipStream_t st);
+int logit_table_catch_up(int B, int V, uint32_t* table, int32_t* counted_len, const int32_t* need, const int64_t* gen_tokens,
+                         int gen_cap, const int32_t* gen_lens, hipStream_t st);
+int process_logits(const f16* logits, f16* out, int T, int V, const uint32_t* table, const int32_t* slot_ids,
+                   const int32_t* active_lens, const f16* rep, const f16* freq, const f16* pres, const int32_t* min_tokens,
+                   const int32_t* gen_base, const int32_t* gen_lens, const int32_t* stop_ids, const int32_t* n_stop,
+                   const int64_t* draft_ids, int64_t di_sb, int64_t di_sk, int rows_per_seq, int j_base, int nslots,
+                   int stop_width, hipStream_t st);
 int typical_acceptance_sample(const float* target_probs, const int64_t* draft_ids, const int64_t* bonus_ids,
                               float posterior_threshold, float posterior_alpha, int B, int k, int V, int64_t di_sb,
                               int64_t di_sk, int64_t bonus_stride, int64_t* out_tokens, uint8_t* accepted, int64_t* recovered,

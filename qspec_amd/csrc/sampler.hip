@@ -561,9 +561,14 @@ __global__ __launch_bounds__(1024) void topk_hist_kernel(const f16* __restrict__
         }
     }
 }
+// MINP (_apply_min_p, sampler.py:416-430, which runs behind top-k / top-p): a token whose probability is below min_p x the row's
+// largest is masked.  p_v / p_max = exp(l_v - max) whatever the denominator and whatever top-k / top-p masked, so it is one more
+// boundary in key order: the first position (descending) whose qexpf(l - max) < min_p, and everything below it.  The <false>
+// instantiation is the kernel as it always was.
+template <bool MINP>
 __global__ __launch_bounds__(1024) void topk_select_kernel(uint32_t* __restrict__ hist, const float* __restrict__ temperature,
                                                             const int32_t* __restrict__ top_k, const float* __restrict__ top_p,
-                                                            TkRow* __restrict__ rows, int V) {
+                                                            const float* __restrict__ min_p, TkRow* __restrict__ rows, int V) {
     __shared__ uint32_t s_cnt[16];
     __shared__ double s_mass[16];
     __shared__ uint32_t s_u[4];
@@ -644,6 +649,7 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(uint32_t* __restrict_
     if (tid == 0) {
         s_u[0] = 0xFFFFFFFFu;   // descending position of the top-k key
         s_u[1] = 0xFFFFFFFFu;   // descending position of the first key top-p masks
+        s_u[2] = 0xFFFFFFFFu;   // descending position of the first key min_p masks
     }
     __syncthreads();
     // (a) top-k: the key at which the descending cumulative count reaches k; Z_k = the mass down to and including it.
@@ -697,9 +703,23 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(uint32_t* __restrict_
         }
         if (best != 0xFFFFFFFFu) atomicMin(&s_u[1], best);
     }
+    if (MINP) {
+        // (b') min_p: every thread offers its first non-empty key with qexpf(l - max) < min_p (the row maximum has 1.0 and
+        // min_p <= 1: it is never masked); greedy rows have none (SamplingParams resets min_p for them, sampling_params.py:344)
+        const float mp = (min_p && !greedy) ? min_p[t] : 0.0f;
+        if (mp > 0.0f && c_loc) {
+            uint32_t best = 0xFFFFFFFFu;
+#pragma unroll
+            for (int j = 0; j < 64; j++)
+                if (cnt[j] && best == 0xFFFFFFFFu && 64u * tid + j != pos_max && qexpf(tk_val(k_hi - j) / temp - mx) < mp)
+                    best = 64u * tid + j;
+            if (best != 0xFFFFFFFFu) atomicMin(&s_u[2], best);
+        }
+    }
     __syncthreads();
     const uint32_t pos_p = s_u[1];                                       // first masked position, or none
-    const uint32_t pos_last = pos_p == 0xFFFFFFFFu ? pos_k : min(pos_k, pos_p - 1);   // last kept position (descending)
+    uint32_t pos_last = pos_p == 0xFFFFFFFFu ? pos_k : min(pos_k, pos_p - 1);   // last kept position (descending)
+    if (MINP && s_u[2] != 0xFFFFFFFFu) pos_last = min(pos_last, s_u[2] - 1);
     // (c) the final denominator: the mass of positions <= pos_last (pos_last itself may be an empty key: the position just
     // above the first masked one); the thread whose 64 positions contain pos_last walks and publishes it
     if ((pos_last >> 6) == (uint32_t)tid) {
@@ -787,7 +807,7 @@ size_t sample_ws_bytes(int rows) {
 static bool g_tk_hist_attr = false;   // topk_hist_kernel's LDS attribute is set (shared by both instantiations)
 template <bool SEEDED>
 static int sample_top_k_top_p_impl(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
-                                   const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
+                                   const float* min_p, const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
                                    int64_t* token, int64_t token_stride, int T, int V, SeedRows sr, void* ws, hipStream_t st) {
     if (T == 0) return 0;
     uint32_t* hist = reinterpret_cast<uint32_t*>(ws);
@@ -800,7 +820,10 @@ static int sample_top_k_top_p_impl(const f16* logits, const float* temperature, 
         g_tk_hist_attr = true;
     }
     hipLaunchKernelGGL(topk_hist_kernel, dim3((V + QS_TK_HCHUNK - 1) / QS_TK_HCHUNK, T), dim3(1024), QS_TK_KEYS * 2, st, logits, hist, V);
-    hipLaunchKernelGGL(topk_select_kernel, dim3(T), dim3(1024), 0, st, hist, temperature, top_k, top_p, rows, V);
+    if (min_p)
+        hipLaunchKernelGGL(topk_select_kernel<true>, dim3(T), dim3(1024), 0, st, hist, temperature, top_k, top_p, min_p, rows, V);
+    else
+        hipLaunchKernelGGL(topk_select_kernel<false>, dim3(T), dim3(1024), 0, st, hist, temperature, top_k, top_p, nullptr, rows, V);
     hipLaunchKernelGGL(topk_write_kernel<SEEDED>, dim3(QS_SM_CHUNKS, T), dim3(256), 0, st, logits, rows, exponential, seed, offset,
                        rng_state, probs, part_a, V, sr);
     hipLaunchKernelGGL(topk_token_kernel, dim3(1), dim3(256), 0, st, part_a, token, token_stride, rng_state, T);
@@ -809,8 +832,8 @@ static int sample_top_k_top_p_impl(const f16* logits, const float* temperature, 
 int sample_top_k_top_p(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
                        const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
                        int64_t* token, int64_t token_stride, int T, int V, void* ws, hipStream_t st) {
-    return sample_top_k_top_p_impl<false>(logits, temperature, top_k, top_p, exponential, seed, offset, rng_state, probs, token,
-                                          token_stride, T, V, SeedRows{}, ws, st);
+    return sample_top_k_top_p_impl<false>(logits, temperature, top_k, top_p, nullptr, exponential, seed, offset, rng_state, probs,
+                                          token, token_stride, T, V, SeedRows{}, ws, st);
 }
 int sample_top_k_top_p_seeded(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
                               const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
@@ -821,8 +844,198 @@ int sample_top_k_top_p_seeded(const f16* logits, const float* temperature, const
         j_base + rows_per_seq > 65536 || draw_stream < 1 || draw_stream > 0x7FFF)
         return -1;
     const SeedRows sr{seq_seeds, seq_seeded, base_pos, rows_per_seq, j_base, (uint32_t)draw_stream};
-    return sample_top_k_top_p_impl<true>(logits, temperature, top_k, top_p, exponential, seed, offset, rng_state, probs, token,
-                                         token_stride, T, V, sr, ws, st);
+    return sample_top_k_top_p_impl<true>(logits, temperature, top_k, top_p, nullptr, exponential, seed, offset, rng_state, probs,
+                                         token, token_stride, T, V, sr, ws, st);
+}
+// min_p [T] fp32 per row (NULL: none -- the selection kernel of the entries above); everything else as there
+int sample_top_k_top_p_min_p(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
+                             const float* min_p, const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state,
+                             float* probs, int64_t* token, int64_t token_stride, int T, int V, void* ws, hipStream_t st) {
+    return sample_top_k_top_p_impl<false>(logits, temperature, top_k, top_p, min_p, exponential, seed, offset, rng_state, probs,
+                                          token, token_stride, T, V, SeedRows{}, ws, st);
+}
+int sample_top_k_top_p_min_p_seeded(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
+                                    const float* min_p, const float* exponential, uint64_t seed, uint64_t offset,
+                                    uint64_t* rng_state, float* probs, int64_t* token, int64_t token_stride, int T, int V,
+                                    const int64_t* seq_seeds, const int32_t* seq_seeded, const int32_t* base_pos, int nseq,
+                                    int rows_per_seq, int j_base, int draw_stream, void* ws, hipStream_t st) {
+    if (!seq_seeds || !seq_seeded || !base_pos || rows_per_seq < 1 || (int64_t)nseq * rows_per_seq < T || j_base < 0 ||
+        j_base + rows_per_seq > 65536 || draw_stream < 1 || draw_stream > 0x7FFF)
+        return -1;
+    const SeedRows sr{seq_seeds, seq_seeded, base_pos, rows_per_seq, j_base, (uint32_t)draw_stream};
+    return sample_top_k_top_p_impl<true>(logits, temperature, top_k, top_p, min_p, exponential, seed, offset, rng_state, probs,
+                                         token, token_stride, T, V, sr, ws, st);
+}
+
+// ---------------------------------------------------------------- logit processors
+// Sampler.forward's steps in front of the temperature (vllm/model_executor/layers/sampler.py:258-266): _apply_min_tokens_penalty
+// (:338-384) and apply_penalties (vllm/model_executor/layers/utils.py:24-57), per ROW of a speculative cycle: row j of a sequence
+// is processed exactly as the non-speculative sampler would process that position given the same prefix -- prompt tokens, the
+// outputs committed before the cycle, the in-flight draft tokens d_1 .. d_j, generated length = committed + j.
+//
+// tok_table[slot][V], one u32 per (slot, token): bit 31 = the token occurs in the prompt, low 31 bits = how often it occurs in
+// the outputs counted so far.  counted_len[slot] = how many of the slot's committed tokens gen_tokens[slot][0 .. gen_lens) are in
+// the table (outputs a re-admitted request had before its admission are counted by logit_table_set_prompt and live in the table
+// only).
+// INVARIANT: catch-up is driven by gen_lens alone -- it adds gen_tokens[slot][counted_len .. gen_len) and sets counted_len =
+// gen_len -- so it is idempotent, and a cycle re-run by recover() needs no rollback: the failed cycle's catch-up left counted_len
+// = gen_len at the START of that cycle, spec_snapshot(restore) brings gen_lens back to exactly that value, and the re-run's
+// catch-up finds nothing to add.  (The tokens the failed cycle committed were never counted: counting happens at the head of the
+// NEXT cycle.)
+#define QS_LP_MAX_STOP 16      // QS_MAX_STOP_IDS of include/qspec_hip.h
+#define QS_LP_MAX_INFLIGHT 64  // in-flight draft tokens a row can see (j_base + rows_per_seq - 1)
+#define QS_LP_CHUNK 2048       // logits per workgroup: 256 threads x 8
+__global__ __launch_bounds__(1024) void logit_table_set_prompt_kernel(uint32_t* __restrict__ row, int V,
+                                                                       const int64_t* __restrict__ prompt, int n_prompt,
+                                                                       const int64_t* __restrict__ outputs, int n_out,
+                                                                       int32_t* __restrict__ counted_len) {
+    // ONE workgroup: clear the row, then mark / count (integer atomics: the result does not depend on the order)
+    for (int v = threadIdx.x; v < V; v += blockDim.x) row[v] = 0u;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_prompt; i += blockDim.x) {
+        const int64_t t = prompt[i];
+        if (t >= 0 && t < V) atomicOr(row + t, 0x80000000u);
+    }
+    for (int i = threadIdx.x; i < n_out; i += blockDim.x) {
+        const int64_t t = outputs[i];
+        if (t >= 0 && t < V) atomicAdd(row + t, 1u);
+    }
+    if (threadIdx.x == 0) *counted_len = 0;
+}
+int logit_table_set_prompt(uint32_t* table, int V, int slot, const int64_t* prompt, int n_prompt, const int64_t* outputs,
+                           int n_out, int32_t* counted_len, hipStream_t st) {
+    hipLaunchKernelGGL(logit_table_set_prompt_kernel, dim3(1), dim3(1024), 0, st, table + (size_t)slot * V, V, prompt, n_prompt,
+                       outputs, n_out, counted_len + slot);
+    return 0;
+}
+// One thread per slot walks its new tokens in order (k + 1 at most in the steady state): plain loads and stores, no atomics,
+// deterministic.  need[slot] == 0: the slot keeps no counts (its penalties are neutral) and is left alone.
+__global__ void logit_table_catch_up_kernel(int B, int V, uint32_t* __restrict__ table, int32_t* __restrict__ counted_len,
+                                            const int32_t* __restrict__ need, const int64_t* __restrict__ gen_tokens, int gen_cap,
+                                            const int32_t* __restrict__ gen_lens) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B || !need[b]) return;
+    const int hi = min(gen_lens[b], gen_cap);
+    int lo = counted_len[b];
+    if (lo < 0) lo = 0;
+    if (hi <= lo) return;   // nothing new (or gen_lens went back: a freed slot; admission rebuilds the row)
+    uint32_t* row = table + (size_t)b * V;
+    for (int i = lo; i < hi; i++) {
+        const int64_t t = gen_tokens[(size_t)b * gen_cap + i];
+        if (t >= 0 && t < V) row[t] = row[t] + 1u;
+    }
+    counted_len[b] = hi;
+}
+int logit_table_catch_up(int B, int V, uint32_t* table, int32_t* counted_len, const int32_t* need, const int64_t* gen_tokens,
+                         int gen_cap, const int32_t* gen_lens, hipStream_t st) {
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(logit_table_catch_up_kernel, dim3((B + 63) / 64), dim3(64), 0, st, B, V, table, counted_len, need,
+                       gen_tokens, gen_cap, gen_lens);
+    return 0;
+}
+// One element, the reference's steps in the reference's order with the reference's roundings (every fp16 op of torch is the
+// fp32 op on the fp16 operands rounded to fp16; f2h keeps hipcc from folding two roundings into one):
+//   min_tokens: stop ids -> -inf;  repetition: x > 0 ? x / r : x * r where the token is in prompt or outputs (x <= 0 is evaluated
+//   AFTER the division, as the reference's second masked assignment is; NaN takes neither);  x -= f * fp16(count);
+//   x -= p * (count > 0) -- the products are formed even where the count is 0: a negative penalty gives -0.0 there and
+//   (-0.0) - (-0.0) = +0.0, as in the reference.
+struct LpRow {
+    f16 rep, freq, pres;
+    bool table, stop;     // the slot keeps counts / the row masks its stop ids
+    int n_inflight, n_stop;
+};
+__device__ __forceinline__ f16 lp_element(f16 x, int v, uint32_t w, const LpRow& r, const int64_t* s_inflight, const int32_t* s_stop) {
+    if (r.stop) {
+        for (int i = 0; i < r.n_stop; i++)
+            if (s_stop[i] == v) x = f2h(-__builtin_inff());
+    }
+    if (!r.table) return x;
+    uint32_t cnt = w & 0x7FFFFFFFu;
+    for (int i = 0; i < r.n_inflight; i++) cnt += (s_inflight[i] == (int64_t)v) ? 1u : 0u;
+    const bool seen = (w >> 31) || cnt > 0u;
+    if (seen) {
+        const float rr = h2f(r.rep);
+        if (h2f(x) > 0.0f) x = f2h(h2f(x) / rr);
+        if (h2f(x) <= 0.0f) x = f2h(h2f(x) * rr);
+    }
+    const f16 cnt_h = f2h((float)cnt);
+    x = f2h(h2f(x) - h2f(f2h(h2f(r.freq) * h2f(cnt_h))));
+    x = f2h(h2f(x) - h2f(f2h(h2f(r.pres) * (cnt > 0u ? 1.0f : 0.0f))));
+    return x;
+}
+struct LpArgs {
+    const f16* logits;            // [T, V] raw
+    f16* out;                     // [T, V] processed (out of place)
+    const uint32_t* table;        // [nslots, V]
+    const int32_t* slot_ids;      // [nseq] slot of sequence s, or NULL: s itself
+    const int32_t* active_lens;   // [nslots] or NULL: a slot with active_lens <= 0 is copied through
+    const f16 *rep, *freq, *pres; // [nslots]
+    const int32_t* min_tokens;    // [nslots]
+    const int32_t* gen_base;      // [nslots] outputs the request had before admission
+    const int32_t* gen_lens;      // [nslots] outputs committed since (at the start of the cycle)
+    const int32_t* stop_ids;      // [nslots, stop_width]
+    const int32_t* n_stop;        // [nslots]
+    const int64_t* draft_ids;     // in-flight token i (0-based) of slot b at b * di_sb + i * di_sk; NULL: none
+    int64_t di_sb, di_sk;
+    int V, rows_per_seq, j_base, nslots, stop_width;   // stop_width <= QS_LP_MAX_STOP: row width of stop_ids
+};
+// grid (chunks of 2048 logits, rows): 16-byte loads of the logits and of the table words, 16-byte stores; a row is wave-uniform
+// in everything but the element itself.  About 8 B of traffic per element (2 + 4 read, 2 written).
+__global__ __launch_bounds__(256) void process_logits_kernel(LpArgs a) {
+    __shared__ int64_t s_inflight[QS_LP_MAX_INFLIGHT];
+    __shared__ int32_t s_stop[QS_LP_MAX_STOP];
+    const int t = blockIdx.y, seq = t / a.rows_per_seq, j = a.j_base + t % a.rows_per_seq;
+    int slot = a.slot_ids ? a.slot_ids[seq] : seq;
+    const bool slot_ok = slot >= 0 && slot < a.nslots;   // (a row outside the slot arrays is copied through)
+    if (!slot_ok) slot = 0;
+    const int V = a.V;
+    const f16* l = a.logits + (size_t)t * V;
+    f16* o = a.out + (size_t)t * V;
+    LpRow r;
+    r.rep = a.rep[slot]; r.freq = a.freq[slot]; r.pres = a.pres[slot];
+    const bool on = slot_ok && (!a.active_lens || a.active_lens[slot] > 0);
+    r.table = on && !(h2f(r.rep) == 1.0f && h2f(r.freq) == 0.0f && h2f(r.pres) == 0.0f);
+    r.n_stop = min(max(a.n_stop[slot], 0), a.stop_width);
+    r.stop = on && r.n_stop > 0 && a.gen_base[slot] + a.gen_lens[slot] + j < a.min_tokens[slot];
+    r.n_inflight = (r.table && a.draft_ids) ? min(j, QS_LP_MAX_INFLIGHT) : 0;
+    if ((int)threadIdx.x < r.n_inflight) s_inflight[threadIdx.x] = a.draft_ids[slot * a.di_sb + threadIdx.x * a.di_sk];
+    if ((int)threadIdx.x < r.n_stop) s_stop[threadIdx.x] = a.stop_ids[slot * a.stop_width + threadIdx.x];
+    __syncthreads();
+    const uint32_t* w = a.table + (size_t)slot * V;
+    const int lo = blockIdx.x * QS_LP_CHUNK, v0 = lo + 8 * (int)threadIdx.x;
+    if (v0 >= V) return;
+    if (V % 8 == 0) {   // rows are 16-byte aligned: one f16x8 per thread (v0 + 8 <= V follows from V % 8 == 0)
+        f16x8 x = *reinterpret_cast<const f16x8*>(l + v0);
+        if (r.table || r.stop) {
+            u32x4 w0 = u32x4{0u, 0u, 0u, 0u}, w1 = w0;
+            if (r.table) {
+                w0 = *reinterpret_cast<const u32x4*>(w + v0);
+                w1 = *reinterpret_cast<const u32x4*>(w + v0 + 4);
+            }
+#pragma unroll
+            for (int e = 0; e < 8; e++) x[e] = lp_element(x[e], v0 + e, e < 4 ? w0[e] : w1[e - 4], r, s_inflight, s_stop);
+        }
+        *reinterpret_cast<f16x8*>(o + v0) = x;
+    } else {
+        const int hi = min(V, v0 + 8);
+        for (int v = v0; v < hi; v++) {
+            f16 x = l[v];
+            if (r.table || r.stop) x = lp_element(x, v, r.table ? w[v] : 0u, r, s_inflight, s_stop);
+            o[v] = x;
+        }
+    }
+}
+int process_logits(const f16* logits, f16* out, int T, int V, const uint32_t* table, const int32_t* slot_ids,
+                   const int32_t* active_lens, const f16* rep, const f16* freq, const f16* pres, const int32_t* min_tokens,
+                   const int32_t* gen_base, const int32_t* gen_lens, const int32_t* stop_ids, const int32_t* n_stop,
+                   const int64_t* draft_ids, int64_t di_sb, int64_t di_sk, int rows_per_seq, int j_base, int nslots,
+                   int stop_width, hipStream_t st) {
+    if (T == 0) return 0;
+    if (stop_width < 0 || stop_width > QS_LP_MAX_STOP || nslots < 1 || rows_per_seq < 1 || j_base < 0 || j_base + rows_per_seq - 1 > QS_LP_MAX_INFLIGHT) return -1;
+    LpArgs a{logits, out, table, slot_ids, active_lens, rep, freq, pres, min_tokens, gen_base, gen_lens, stop_ids, n_stop,
+             draft_ids, di_sb, di_sk, V, rows_per_seq, j_base, nslots, stop_width};
+    hipLaunchKernelGGL(process_logits_kernel, dim3((V + QS_LP_CHUNK - 1) / QS_LP_CHUNK, T), dim3(256), 0, st, a);
+    return 0;
 }
 
 // advance_step_flashattn_kernel without the CUDA-graph padding branch (num_seqs == num_queries).

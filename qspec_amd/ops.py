@@ -739,13 +739,17 @@ def new_sample_workspace(rows: int, device):
 
 def sample_top_k_top_p(logits, probs, token, temperature=None, top_k=None, top_p=None, exponential=None, seed: int = 0,
                        offset: int = 0, rng_state=None, workspace=None, seq_seeds=None, seq_seeded=None, base_pos=None,
-                       rows_per_seq: int = 1, j_base: int = 0, draw_stream: int = 2):
+                       rows_per_seq: int = 1, j_base: int = 0, draw_stream: int = 2, min_p=None):
     """Sampler.forward for non-greedy rows (sampler.py:216-316): temperature, top-k / top-p masking, softmax, multinomial by
     exponential noise.  temperature / top_p [T] fp32, top_k [T] int32 on the device (None: 1.0 / off).
     seq_seeds int64 / seq_seeded int32 / base_pos int32, one entry per SEQUENCE (all or none): row t belongs to sequence
     t // rows_per_seq, and rows of seeded sequences draw from Philox keyed by (seed, base_pos, draw_stream,
-    j_base + t % rows_per_seq) alone -- qspec_sample_top_k_top_p_seeded (include/qspec_hip.h)."""
+    j_base + t % rows_per_seq) alone -- qspec_sample_top_k_top_p_seeded (include/qspec_hip.h).
+    min_p [T] fp32 (None: the entry points without it): _apply_min_p behind top-k / top-p, tokens whose probability is below
+    min_p x the row's largest are masked -- qspec_sample_top_k_top_p_min_p(_seeded)."""
     T, V = logits.shape
+    if min_p is not None and min_p.numel() < T:
+        raise RuntimeError(f"min_p has {min_p.numel()} entries, {T} rows need one each")
     ws = workspace if workspace is not None else sample_workspace(T, logits.device)
     nseq = (T + rows_per_seq - 1) // max(1, rows_per_seq)
     seeded = _seq_seed_args(seq_seeds, seq_seeded, base_pos, nseq)
@@ -753,11 +757,79 @@ def sample_top_k_top_p(logits, probs, token, temperature=None, top_k=None, top_p
             _opt(top_k, "top_k", _I32), _opt(top_p, "top_p", _F32), _opt(exponential, "exponential", _F32), seed, offset,
             _opt(rng_state, "rng_state", _I64), _chk(probs, "probs", _F32), token.data_ptr(), token.stride(0) if token.dim() else 1,
             T, V)
+    suffix = ""
+    if min_p is not None:   # (the min_p array sits behind top_p in the argument list)
+        args = args[:4] + (_chk(min_p, "min_p", _F32),) + args[4:]
+        suffix = "_min_p"
     if seeded is None:
-        _call("qspec_sample_top_k_top_p", *args, ws.data_ptr(), _stream())
+        _call("qspec_sample_top_k_top_p" + suffix, *args, ws.data_ptr(), _stream())
     else:
-        _call("qspec_sample_top_k_top_p_seeded", *args, *seeded, seq_seeds.numel(), rows_per_seq, j_base, draw_stream,
-              ws.data_ptr(), _stream())
+        _call("qspec_sample_top_k_top_p" + suffix + "_seeded", *args, *seeded, seq_seeds.numel(), rows_per_seq, j_base,
+              draw_stream, ws.data_ptr(), _stream())
+
+
+# ------------------------------------------------------------------ logit processors (include/qspec_hip.h, "logit processors")
+MAX_STOP_IDS = 16   # QS_MAX_STOP_IDS
+
+
+def new_logit_table(num_slots: int, vocab: int, device):
+    """(tok_table [num_slots, vocab] int32 -- bit 31: in the prompt, low bits: output count --, counted_len [num_slots] int32)."""
+    return (torch.zeros(num_slots, vocab, dtype=_I32, device=device), torch.zeros(num_slots, dtype=_I32, device=device))
+
+
+def logit_table_set_prompt(tok_table, counted_len, slot: int, prompt_ids, output_ids=None):
+    """Rebuild the table row of `slot` at admission: prompt_ids / output_ids int64 device tensors (output_ids: the outputs a
+    re-admitted request already has); counted_len[slot] = 0."""
+    B, V = tok_table.shape
+    n_out = 0 if output_ids is None else output_ids.numel()
+    _call("qspec_logit_table_set_prompt", _chk(tok_table, "tok_table", _I32), _chk(counted_len, "counted_len", _I32), B, V,
+          int(slot), _chk(prompt_ids, "prompt_ids", _I64), prompt_ids.numel(),
+          _chk(output_ids, "output_ids", _I64) if n_out else None, n_out, _stream())
+
+
+def logit_table_catch_up(tok_table, counted_len, need_counts, gen_tokens, gen_lens):
+    """Count gen_tokens[slot][counted_len .. gen_lens) of every slot with need_counts != 0; counted_len = gen_lens.  Idempotent."""
+    B, V = tok_table.shape
+    if gen_tokens.shape[0] < B or gen_lens.numel() < B or need_counts.numel() < B or counted_len.numel() < B:
+        raise RuntimeError("the per-slot arrays are shorter than the table")
+    _call("qspec_logit_table_catch_up", _chk(tok_table, "tok_table", _I32), _chk(counted_len, "counted_len", _I32),
+          _chk(need_counts, "need_counts", _I32), B, V, _chk(gen_tokens, "gen_tokens", _I64), gen_tokens.shape[1],
+          _chk(gen_lens, "gen_lens", _I32), _stream())
+
+
+def process_logits(logits, out, tok_table, repetition, frequency, presence, min_tokens, gen_base, gen_lens, stop_ids,
+                   num_stop_ids, draft_ids=None, rows_per_seq: int = 1, j_base: int = 0, slot_ids=None, active_lens=None):
+    """_apply_min_tokens_penalty + apply_penalties per row (sampler.py:258-266), out of place: out [T, V] fp16.  Row t belongs to
+    sequence t // rows_per_seq (slot slot_ids[sequence] or the sequence index) with j = j_base + t % rows_per_seq and sees the
+    in-flight tokens draft_ids[0 .. j, slot] (draft_ids [n, num_slots] int64, step-major as the engine keeps them; any strides).
+    The per-slot arrays are device tensors read when the call runs."""
+    T, V = logits.shape
+    B = tok_table.shape[0]
+    if tok_table.shape[1] != V or out.shape != logits.shape:
+        raise RuntimeError("tok_table / out do not match the logits")
+    for t, name in ((repetition, "repetition"), (frequency, "frequency"), (presence, "presence"), (min_tokens, "min_tokens"),
+                    (gen_base, "gen_base"), (gen_lens, "gen_lens"), (num_stop_ids, "num_stop_ids")):
+        if t.numel() < B:
+            raise RuntimeError(f"{name} has {t.numel()} entries, the table has {B} slots")
+    if stop_ids.dim() != 2 or stop_ids.shape[0] < B:
+        raise RuntimeError("stop_ids must be [num_slots, width]")
+    nseq = (T + rows_per_seq - 1) // max(1, rows_per_seq)
+    if slot_ids is not None and slot_ids.numel() < nseq:
+        raise RuntimeError(f"slot_ids has {slot_ids.numel()} entries, {nseq} sequences need one each")
+    if active_lens is not None and active_lens.numel() < B:
+        raise RuntimeError("active_lens is shorter than the table")
+    n_draft, di_sb, di_sk, di_ptr = 0, 0, 0, None
+    if draft_ids is not None:
+        if draft_ids.dim() != 2 or draft_ids.shape[1] < B or draft_ids.dtype != _I64 or not draft_ids.is_cuda:
+            raise RuntimeError("draft_ids must be an int64 [steps, num_slots] GPU tensor")
+        n_draft, di_sk, di_sb, di_ptr = draft_ids.shape[0], draft_ids.stride(0), draft_ids.stride(1), draft_ids.data_ptr()
+    _call("qspec_process_logits", _chk(logits, "logits", _F16), _chk(out, "out", _F16), T, V, _chk(tok_table, "tok_table", _I32),
+          B, _opt(slot_ids, "slot_ids", _I32), _opt(active_lens, "active_lens", _I32), _chk(repetition, "repetition", _F16),
+          _chk(frequency, "frequency", _F16), _chk(presence, "presence", _F16), _chk(min_tokens, "min_tokens", _I32),
+          _chk(gen_base, "gen_base", _I32), _chk(gen_lens, "gen_lens", _I32), _chk(stop_ids, "stop_ids", _I32),
+          _chk(num_stop_ids, "num_stop_ids", _I32), stop_ids.shape[1], di_ptr, n_draft, di_sb, di_sk, rows_per_seq, j_base,
+          _stream())
+    return out
 
 
 def typical_acceptance_sample(target_with_bonus_probs, bonus_token_ids, draft_token_ids, posterior_threshold: float,

@@ -169,10 +169,35 @@ class QSpecEngine:
         self._mode_sampling = False
         self._graph_s: Optional[torch.cuda.CUDAGraph] = None       # the cycle with the sampling front end
         self._graph_draft_s: Optional[torch.cuda.CUDAGraph] = None
+        # ---- logit processors per slot (the rest of Sampler.forward, sampler.py:258-278): min_p, presence / frequency /
+        # repetition penalties, min_tokens.  Device arrays read at replay; penalties in fp16, the dtype the reference holds
+        # them in.  While no occupied slot has a non-neutral value the engine replays exactly the two cycles above; as soon
+        # as one has, it replays a THIRD captured cycle: the sampling cycle with the token-table catch-up at its head and the
+        # logits pre-pass (ops.process_logits) in front of every sampler call.  Every row is processed as the non-speculative
+        # sampler would process that position: prompt, committed outputs + the in-flight draft tokens d_1 .. d_j, generated
+        # length committed + j (include/qspec_hip.h, "logit processors").
+        # All of it is allocated on first use (_ensure_processing; an engine that never sees such a request holds none of
+        # it): the per-slot parameter arrays, the token table [B, V] (bit 31: in the prompt, low bits: output count),
+        # counted_len [B] (how many of gen_tokens[b][:gen_lens[b]] the table holds) and the processed-logits buffers.
+        # INVARIANT: the catch-up at the head of a cycle is driven by gen_lens alone, so recover() -- which restores gen_lens
+        # to the value it had at the start of the failed cycle, i.e. to counted_len -- re-runs it without double counting
+        self._lp_host = None                                       # per slot (min_p, pres, freq, rep, min_tokens, stop ids)
+        self.tok_table = None
+        self._mode_processing = False
+        self._graph_p: Optional[torch.cuda.CUDAGraph] = None       # the sampling cycle with the logit processors
+        self._graph_draft_p: Optional[torch.cuda.CUDAGraph] = None
         # test hooks: injected random draws for the rejection sampler (eager mode only)
         self.inject_uniform: Optional[torch.Tensor] = None
         self.inject_exponential: Optional[torch.Tensor] = None
         self._prefill_scratch: Optional[Scratch] = None
+
+    _LP_NEUTRAL = (0.0, 0.0, 0.0, 1.0, 0, ())   # min_p, presence, frequency, repetition, min_tokens, stop ids
+    _lp_host: Optional[list] = None             # None until a request first uses a logit processor
+    tok_table: Optional[torch.Tensor] = None
+    _mode_processing = False
+
+    def _lp(self, slot: int):
+        return self._LP_NEUTRAL if self._lp_host is None else self._lp_host[slot]
 
     # the embedding lookups of the cycle's four forwards ride in the bookkeeping launches in front of them (5 launches less)
     EMBED_IN_BOOKKEEPING = os.environ.get("QSPEC_EMBED_IN_BOOKKEEPING", "1") != "0"
@@ -188,8 +213,11 @@ class QSpecEngine:
 
     @torch.no_grad()
     def add_sequences_to(self, slots: Sequence[int], prompts: Sequence[Sequence[int]],
-                         block_tables: Optional[Sequence[Optional[Sequence[int]]]] = None) -> None:
-        """Admit several requests at once: one W4A16 forward over the concatenated prompts (flash-attn varlen form)."""
+                         block_tables: Optional[Sequence[Optional[Sequence[int]]]] = None,
+                         num_prompt_tokens: Optional[Sequence[Optional[int]]] = None) -> None:
+        """Admit several requests at once: one W4A16 forward over the concatenated prompts (flash-attn varlen form).
+        num_prompt_tokens[i] (None: all of it): how many tokens of prompts[i] are the request's PROMPT -- a preempted
+        request comes back with prompt + outputs as one token list, and the penalties / min_tokens tell the two apart."""
         cfg, dev = self.cfg, self.device
         n = len(slots)
         if n == 0:
@@ -209,8 +237,13 @@ class QSpecEngine:
             if T < 1 or T + 1 > min(cap, self.max_model_len):
                 raise ValueError(f"prompt of {T} tokens does not fit slot {b} (capacity {cap} tokens, max_model_len "
                                  f"{self.max_model_len})" + ("" if cap else ": the request brought no block table"))
+        npts = [None] * n if num_prompt_tokens is None else list(num_prompt_tokens)
+        for i in range(n):
+            if npts[i] is not None and not 1 <= npts[i] <= len(prompts[i]):
+                raise ValueError(f"num_prompt_tokens {npts[i]} outside 1..{len(prompts[i])}")
         if n == 1:
-            self.add_sequence(slots[0], prompts[0], None if block_tables is None else block_tables[0])
+            self.add_sequence(slots[0], prompts[0], None if block_tables is None else block_tables[0],
+                              num_prompt_tokens=npts[0])
             return
         if sum(len(p) for p in prompts) > self.PREFILL_TOKEN_BUDGET:
             # several passes of at most PREFILL_TOKEN_BUDGET tokens (measured: 4 x 512 tokens in one pass 37 ms vs 49 ms
@@ -219,7 +252,8 @@ class QSpecEngine:
             for i in range(n + 1):
                 if i == n or (group and tokens + len(prompts[i]) > self.PREFILL_TOKEN_BUDGET):
                     self.add_sequences_to([slots[j] for j in group], [prompts[j] for j in group],
-                                          None if block_tables is None else [block_tables[j] for j in group])
+                                          None if block_tables is None else [block_tables[j] for j in group],
+                                          [npts[j] for j in group])
                     group, tokens = [], 0
                 if i < n:
                     group.append(i)
@@ -242,6 +276,8 @@ class QSpecEngine:
         logits = self.model.compute_logits(hs[last].contiguous(), s)
         probs = torch.empty(n, cfg.vocab_size, dtype=torch.float32, device=dev)
         tok = torch.empty(n, dtype=torch.int64, device=dev)
+        for i, b in enumerate(slots):
+            self._admit_tokens(b, prompts[i], npts[i])
         self._first_token(logits, probs, tok, list(slots), lens)
         for i, (b, T) in enumerate(zip(slots, lens)):
             self.seq_lens[b] = T + 1
@@ -256,7 +292,7 @@ class QSpecEngine:
 
     @torch.no_grad()
     def add_sequence(self, slot: int, prompt: Sequence[int], block_table: Optional[Sequence[int]] = None,
-                     sync: bool = True) -> None:
+                     sync: bool = True, num_prompt_tokens: Optional[int] = None) -> None:
         """Admit a request into an empty slot: scorer-only W4A16 prompt pass (the proposer never runs on prefill,
         spec_decode_worker.py:699); the first generated token is the target's greedy token."""
         cfg, dev, b = self.cfg, self.device, slot
@@ -264,6 +300,8 @@ class QSpecEngine:
             raise ValueError(f"slot {b} outside the captured batch of {self.B}")
         if self._len_ub[b] != 0:
             raise ValueError(f"slot {b} is occupied; free_slot() it first")
+        if num_prompt_tokens is not None and not 1 <= num_prompt_tokens <= len(prompt):
+            raise ValueError(f"num_prompt_tokens {num_prompt_tokens} outside 1..{len(prompt)}")
         if block_table is not None:
             self.set_block_table(b, block_table)
         T = len(prompt)
@@ -283,6 +321,7 @@ class QSpecEngine:
         logits = self.model.compute_logits(hs[T - 1:T], s)
         probs = torch.empty(1, cfg.vocab_size, dtype=torch.float32, device=dev)
         tok = torch.empty(1, dtype=torch.int64, device=dev)
+        self._admit_tokens(b, prompt, num_prompt_tokens)
         self._first_token(logits, probs, tok, [b], [T])
         self.seq_lens[b] = T + 1
         self.last_token[b] = tok[0]
@@ -298,12 +337,17 @@ class QSpecEngine:
     def _first_token(self, logits, probs, tok, slots: List[int], prompt_lens: List[int]) -> None:
         """The target's first token of freshly admitted prompts: greedy, or sampled with the slots' parameters (a seeded
         request: target stream, j = 0, base position = its prompt length)."""
+        processed = any(self._lp(b) != self._LP_NEUTRAL for b in slots)
+        if processed:   # position 0 of the request: j = 0, no in-flight tokens (gen_lens of a fresh slot is 0)
+            logits = self._process(logits, torch.empty_like(logits), rows_per_seq=1, j_base=0, draft_ids=None, active_lens=None,
+                                   slot_ids=torch.tensor(slots, dtype=torch.int32, device=self.device))
         if all(self._samp_host[b][0] < 1e-5 for b in slots):
             ops.softmax_argmax(logits, probs, tok)
             return
         idx = torch.tensor(slots, dtype=torch.int64, device=self.device)
         ops.sample_top_k_top_p(logits, probs, tok, self.samp_temp[idx].contiguous(), self.samp_topk[idx].contiguous(),
                                self.samp_topp[idx].contiguous(), rng_state=self.sampler.rng_state,
+                               min_p=self.samp_minp[idx].contiguous() if processed else None,
                                seq_seeds=self.seq_seed[idx].contiguous(), seq_seeded=self.seq_seeded[idx].contiguous(),
                                base_pos=torch.tensor(prompt_lens, dtype=torch.int32, device=self.device),
                                rows_per_seq=1, j_base=0, draw_stream=2)
@@ -330,13 +374,57 @@ class QSpecEngine:
         self.n_active = sum(1 for v in self._len_ub if v > 0)
 
     def set_sampling_params(self, slot: int, temperature: float = 0.0, top_k: int = -1, top_p: float = 1.0,
-                            seed: Optional[int] = None) -> None:
+                            seed: Optional[int] = None, min_p: float = 0.0, presence_penalty: float = 0.0,
+                            frequency_penalty: float = 0.0, repetition_penalty: float = 1.0, min_tokens: int = 0,
+                            stop_token_ids: Sequence[int] = ()) -> None:
         """The request in `slot` samples with these parameters (vllm/sampling_params.py; temperature < 1e-5 = greedy, for
         which vLLM itself resets top_k / top_p).  seed (SamplingParams.seed, taken mod 2^64): the request's draws depend
         on it and its own positions only; a greedy request makes no draws and ignores it.  Uploaded only when they
-        change; a change never re-captures the graph (the kernels read the seed arrays at replay)."""
-        if temperature < 1e-5:
+        change; a change never re-captures the graph (the kernels read the seed arrays at replay).
+        min_p / presence_penalty / frequency_penalty / repetition_penalty / min_tokens (+ stop_token_ids: every id that may
+        not be emitted before min_tokens tokens were generated, the EOS id included): vllm/sampling_params.py; applied per row
+        of the cycle as the non-speculative sampler would apply them at that position.  They belong to the request: set them
+        BEFORE its admission (the admission builds the slot's token table).  Refused with ValueError, nothing enqueued: more
+        than 16 stop ids, min_p outside [0, 1], repetition_penalty <= 0, min_tokens < 0, non-finite penalties."""
+        stop = tuple(int(t) for t in stop_token_ids)
+        vals = (float(min_p), float(presence_penalty), float(frequency_penalty), float(repetition_penalty))
+        if len(stop) > ops.MAX_STOP_IDS:
+            raise ValueError(f"{len(stop)} stop token ids: at most {ops.MAX_STOP_IDS} are supported")
+        if not all(v == v and abs(v) != float("inf") for v in vals):
+            raise ValueError("min_p and the penalties must be finite")
+        if not 0.0 <= vals[0] <= 1.0:
+            raise ValueError(f"min_p {min_p} outside [0, 1]")
+        if not vals[3] > 0.0:
+            raise ValueError(f"repetition_penalty {repetition_penalty} must be > 0")
+        if int(min_tokens) < 0:
+            raise ValueError(f"min_tokens {min_tokens} must be >= 0")
+        if temperature < 1e-5:   # (min_p is reset for greedy requests, sampling_params.py:344; the rest applies to them too)
             temperature, top_k, top_p, seed = 0.0, -1, 1.0, None
+            vals = (0.0,) + vals[1:]
+        if int(min_tokens) == 0 or not stop:
+            min_tokens, stop = 0, ()
+        want_lp = vals + (int(min_tokens), stop)
+        if want_lp != self._lp(slot):
+            h = torch.tensor(vals[1:], dtype=torch.float16)   # what the kernels will read
+            if float(h[2]) <= 0.0 or not bool(torch.isfinite(h).all()):
+                raise ValueError("a penalty is outside the fp16 range")
+            need = int(float(h[0]) != 0.0 or float(h[1]) != 0.0 or float(h[2]) != 1.0)
+            if need and self._len_ub[slot] > 0 and not self._lp_needs(slot):
+                raise ValueError(f"slot {slot} is occupied: penalties are set before the request is admitted (its token "
+                                 "table is built at admission)")
+            self._ensure_processing()
+            k1 = self.k + 1
+            self.samp_minp[slot] = vals[0]
+            self.v_samp_minp[slot * k1:(slot + 1) * k1] = vals[0]
+            self.lp_pres[slot] = h[0]; self.lp_freq[slot] = h[1]; self.lp_rep[slot] = h[2]
+            self.lp_min_tokens[slot] = int(min_tokens)
+            row = torch.zeros(ops.MAX_STOP_IDS, dtype=torch.int32)
+            if stop:
+                row[:len(stop)] = torch.tensor(stop, dtype=torch.int64).clamp(-1, 2 ** 31 - 1).to(torch.int32)
+            self.lp_stop_ids[slot].copy_(row.to(self.device))
+            self.lp_n_stop[slot] = len(stop)
+            self.lp_need[slot] = need
+            self._lp_host[slot] = want_lp
         want_seed = None if seed is None else int(seed) % (1 << 64)
         if self._seed_host[slot] != want_seed:
             self.seq_seed[slot] = 0 if want_seed is None else want_seed - (1 << 64) * (want_seed >= 1 << 63)
@@ -354,6 +442,60 @@ class QSpecEngine:
 
     def _sampling_on(self) -> bool:
         return any(self._samp_host[b][0] >= 1e-5 for b in range(self.B) if self._len_ub[b] > 0)
+
+    def _processing_on(self) -> bool:
+        """Some occupied slot has a non-neutral logit-processor value: the cycle is the third graph."""
+        return self._lp_host is not None and any(self._lp_host[b] != self._LP_NEUTRAL for b in range(self.B)
+                                                 if self._len_ub[b] > 0)
+
+    def _lp_needs(self, slot: int) -> bool:
+        """The slot keeps token counts: one of its penalties is non-neutral (in fp16, as the kernels read it)."""
+        _, pres, freq, rp, _, _ = self._lp(slot)
+        h = torch.tensor((pres, freq, rp), dtype=torch.float16)
+        return bool(float(h[0]) != 0.0 or float(h[1]) != 0.0 or float(h[2]) != 1.0)
+
+    def _ensure_processing(self) -> None:
+        if self._lp_host is not None:
+            return
+        B, T, V, dev, i32 = self.B, self.B * (self.k + 1), self.cfg.vocab_size, self.device, torch.int32
+        self.samp_minp = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.v_samp_minp = torch.zeros(T, dtype=torch.float32, device=dev)     # the same, one row per verify token
+        self.lp_rep = torch.ones(B, dtype=torch.float16, device=dev)
+        self.lp_freq = torch.zeros(B, dtype=torch.float16, device=dev)
+        self.lp_pres = torch.zeros(B, dtype=torch.float16, device=dev)
+        self.lp_min_tokens = torch.zeros(B, dtype=i32, device=dev)
+        self.lp_gen_base = torch.zeros(B, dtype=i32, device=dev)   # outputs a re-admitted request had before its admission
+        self.lp_stop_ids = torch.zeros(B, ops.MAX_STOP_IDS, dtype=i32, device=dev)
+        self.lp_n_stop = torch.zeros(B, dtype=i32, device=dev)
+        self.lp_need = torch.zeros(B, dtype=i32, device=dev)       # the slot keeps token counts (a non-neutral penalty)
+        self._gen_base_host = [0] * B
+        self.tok_table, self.counted_len = ops.new_logit_table(B, V, dev)
+        self.proc_logits_d = torch.zeros(B, V, dtype=torch.float16, device=dev)   # draft steps / non-speculative step
+        self.proc_logits_v = torch.zeros(T, V, dtype=torch.float16, device=dev)   # verify rows
+        self._lp_host = [self._LP_NEUTRAL] * B
+
+    def _admit_tokens(self, slot: int, tokens: Sequence[int], num_prompt_tokens: Optional[int]) -> None:
+        """Admission: the outputs the request already has (recomputation) and, for a slot with penalties, its table row."""
+        if self._lp_host is None:
+            return
+        npt = len(tokens) if num_prompt_tokens is None else int(num_prompt_tokens)
+        base = len(tokens) - npt
+        if self._gen_base_host[slot] != base:
+            self.lp_gen_base[slot] = base
+            self._gen_base_host[slot] = base
+        if self._lp_needs(slot):
+            ids = torch.tensor(list(tokens), dtype=torch.int64, device=self.device)
+            ops.logit_table_set_prompt(self.tok_table, self.counted_len, slot, ids[:npt].contiguous(),
+                                       ids[npt:].contiguous() if base else None)
+
+    def _process(self, logits, out, rows_per_seq: int, j_base: int, draft_ids, active_lens, slot_ids=None):
+        T = logits.shape[0]
+        return ops.process_logits(logits, out[:T], self.tok_table, self.lp_rep, self.lp_freq, self.lp_pres, self.lp_min_tokens,
+                                  self.lp_gen_base, self.gen_lens, self.lp_stop_ids, self.lp_n_stop, draft_ids=draft_ids,
+                                  rows_per_seq=rows_per_seq, j_base=j_base, slot_ids=slot_ids, active_lens=active_lens)
+
+    def _catch_up(self) -> None:
+        ops.logit_table_catch_up(self.tok_table, self.counted_len, self.lp_need, self.gen_tokens, self.gen_lens)
 
     def set_block_table(self, slot: int, blocks: Sequence[int]) -> None:
         """The scheduler's block table of the request in `slot` (vLLM SequenceGroupMetadata.block_tables); it must
@@ -419,8 +561,13 @@ class QSpecEngine:
         ops.spec_snapshot(self.seq_lens, self.gen_lens, self.last_token, self.sampler.counters, self.sampler.rng_state,
                           self._snap_i32, self._snap_i64)
 
-    def _cycle_body(self):
+    def _cycle_head(self):
         self._snapshot()
+        if self._mode_processing:   # the tokens committed since the last catch-up enter the table (idempotent: see __init__)
+            self._catch_up()
+
+    def _cycle_body(self):
+        self._cycle_head()
         self._draft_body()
         self._verify_body()
         self._collect_errors()
@@ -459,9 +606,13 @@ class QSpecEngine:
             hs = m.forward(self.d_tokens, self.d_pos, self.kv_caches, self.md_draft, self.scratch_draft, w4a4=True,
                            embedded=emb_d is not None)
             if self._mode_sampling:   # draft tokens are SAMPLED from the processed draft distribution (sampler.py:216-316)
+                extra = {}
+                if self._mode_processing:   # draft step i proposes d_{i+1}: it sees d_1 .. d_i in flight
+                    extra = dict(min_p=self.samp_minp, process=lambda lg, j=i: self._process(
+                        lg, self.proc_logits_d, 1, j, self.draft_ids_kb, self.eff_lens))
                 m.sample(hs, self.scratch_draft, self.draft_probs_kbv[i], self.draft_ids_kb[i], self.samp_temp, self.samp_topk,
                          self.samp_topp, self.sampler.rng_state, shard_vocab=draft_sv, workspace=self._sample_ws_d,
-                         **self._seed_args(rows_per_seq=1, j_base=i, draw_stream=1))
+                         **extra, **self._seed_args(rows_per_seq=1, j_base=i, draw_stream=1))
             else:
                 m.sample_greedy(hs, self.scratch_draft, self.draft_probs_kbv[i], self.draft_ids_kb[i], shard_vocab=draft_sv)
             if i != k - 1:  # _gpu_advance_step (draft_model_runner.py:78-135)
@@ -481,9 +632,13 @@ class QSpecEngine:
         hook = self._verify_logits_hook(draft_ids)
         seeded = {}
         if self._mode_sampling:
+            extra = {}
+            if self._mode_processing:   # verify row j = 0..k sees d_1 .. d_j in flight
+                extra = dict(min_p=self.v_samp_minp, process=lambda lg: self._process(
+                    lg, self.proc_logits_v, k + 1, 0, self.draft_ids_kb, self.eff_lens))
             m.sample(hs, self.scratch_verify, self.target_probs.view(B * (k + 1), -1), self.target_tokens.view(-1),
                      self.v_samp_temp, self.v_samp_topk, self.v_samp_topp, self.sampler.rng_state, shard_vocab=True,
-                     logits_hook=hook, workspace=self._sample_ws_v,
+                     logits_hook=hook, workspace=self._sample_ws_v, **extra,
                      **self._seed_args(rows_per_seq=k + 1, j_base=0, draw_stream=2))
             seeded = self._seed_args()
         else:
@@ -529,9 +684,14 @@ class QSpecEngine:
                                self.d_slots, self.d_ctx)                   # [last token] at position seq_len - 1
         hs = m.forward(self.d_tokens, self.d_pos, self.kv_caches, self.md_draft, self.scratch_draft, w4a4=False)
         logits = m.compute_logits(hs, self.scratch_draft)
-        if self._sampling_on():   # sampled requests sample (a seeded one: target stream, j = 0); greedy rows take the argmax
+        processing = self._processing_on()
+        if processing:   # position j = 0, nothing in flight: catch up with the committed tokens, then the pre-pass
+            self._catch_up()
+            logits = self._process(logits, self.proc_logits_d, 1, 0, None, self.eff_lens)
+        if self._sampling_on() or processing:   # sampled requests sample (a seeded one: target stream, j = 0); greedy rows take the argmax
             ops.sample_top_k_top_p(logits, self.draft_probs_kbv[0], self.draft_ids_kb[0], self.samp_temp, self.samp_topk,
                                    self.samp_topp, rng_state=self.sampler.rng_state, workspace=self._sample_ws_d,
+                                   min_p=self.samp_minp if processing else None,
                                    **self._seed_args(rows_per_seq=1, j_base=0, draw_stream=2))
         else:
             ops.softmax_argmax(logits, self.draft_probs_kbv[0], self.draft_ids_kb[0])
@@ -553,17 +713,19 @@ class QSpecEngine:
         for b in on:                       # until the caller reports / syncs the real numbers: the worst case
             self._len_ub[b] += self.k + 1
             self._gen_ub[b] += self.k + 1
-        self._mode_sampling = self._sampling_on()     # (every rank sees the same requests: the same decision)
+        # (every rank sees the same requests: the same decisions.)  The processed cycle is the sampling cycle + the pre-pass
+        self._mode_processing = self._processing_on()
+        self._mode_sampling = self._mode_processing or self._sampling_on()
         if not self.use_graph:
             self._cycle_body()
             return
-        full, draft = (self._graph_s, self._graph_draft_s) if self._mode_sampling else (self._graph, self._graph_draft)
+        full, draft = self._graphs()
         if full is None and draft is None:
             self._capture()
             if not self.use_graph:
                 self._cycle_body()
                 return
-            full, draft = (self._graph_s, self._graph_draft_s) if self._mode_sampling else (self._graph, self._graph_draft)
+            full, draft = self._graphs()
         if full is not None:
             full.replay()
         else:   # the verify pass could not be captured (its collectives): proposer from its graph, scorer eagerly.
@@ -572,6 +734,15 @@ class QSpecEngine:
             draft.replay()
             self._verify_body()
             self._collect_errors()
+
+    def _graph_names(self):
+        return ("_graph_p", "_graph_draft_p") if self._mode_processing else \
+            ("_graph_s", "_graph_draft_s") if self._mode_sampling else ("_graph", "_graph_draft")
+
+    def _graphs(self):
+        """(whole-cycle graph, draft-only graph) of the current mode: greedy, sampling or processed."""
+        full, draft = self._graph_names()
+        return getattr(self, full), getattr(self, draft)
 
     def _capture(self):
         # warm up outside capture (lazy module loads, LDS attribute), on a side stream as torch requires.
@@ -600,13 +771,10 @@ class QSpecEngine:
             try:   # the proposer has no collectives (replicated under TP): keep its k forwards in a graph
                 gd = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gd):
-                    self._snapshot()
+                    self._cycle_head()
                     self._draft_body()
                 torch.cuda.synchronize()
-                if self._mode_sampling:
-                    self._graph_draft_s = gd
-                else:
-                    self._graph_draft = gd
+                setattr(self, self._graph_names()[1], gd)
                 warnings.warn(f"hipGraph capture of the whole cycle failed ({exc!r}); "
                               "the draft pass replays from a graph, the verify pass runs eagerly")
             except Exception as exc2:
@@ -620,10 +788,7 @@ class QSpecEngine:
         for t, s in zip((self.seq_lens, self.last_token, self.gen_tokens, self.gen_lens, self.sampler.counters,
                          self.sampler.rng_state), state):
             t.copy_(s)
-        if self._mode_sampling:
-            self._graph_s = g
-        else:
-            self._graph = g
+        setattr(self, self._graph_names()[0], g)
 
     # ------------------------------------------------------------------ results
     def generated(self) -> List[List[int]]:

@@ -71,6 +71,13 @@ class SamplingParams:
     temperature: float = 0.0
     top_k: int = -1
     top_p: float = 1.0
+    # the logit processors of Sampler.forward (sampler.py:258-278), applied inside the captured cycle
+    min_p: float = 0.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    repetition_penalty: float = 1.0
+    min_tokens: int = 0
+    stop_token_ids: Optional[List[int]] = None   # (a vLLM object also carries all_stop_token_ids: these + the EOS id)
 
 
 @dataclass
@@ -545,18 +552,26 @@ class SpecDecodeWorker:
         if len(free) < len(prompts):
             raise RuntimeError(f"no free sequence slot for request {prompts[len(free)].request_id}: "
                                f"max_num_seqs={self.max_num_seqs} are running")
-        slots, toks, tables = free[:len(prompts)], [], []
-        for s, b in zip(prompts, slots):
-            seq_id, data = self._only_seq(s)
-            toks.append(data.get_token_ids())
-            tables.append(s.block_tables.get(seq_id) if s.block_tables else None)
-            sp = s.sampling_params   # before the prompt pass: the first token is sampled with them too
-            seed = getattr(sp, "seed", None)   # (forwarded only when set: an engine double need not know the keyword)
-            self.engine.set_sampling_params(b, getattr(sp, "temperature", 0.0) or 0.0, getattr(sp, "top_k", -1) or -1,
-                                            getattr(sp, "top_p", 1.0) if sp is not None else 1.0,
-                                            **({} if seed is None else {"seed": seed}))
+        slots, toks, tables, npts = free[:len(prompts)], [], [], []
         try:
-            self.engine.add_sequences_to(slots, toks, tables)
+            for s, b in zip(prompts, slots):
+                seq_id, data = self._only_seq(s)
+                toks.append(data.get_token_ids())
+                tables.append(s.block_tables.get(seq_id) if s.block_tables else None)
+                sp = s.sampling_params   # before the prompt pass: the first token is sampled with them too
+                seed = getattr(sp, "seed", None)   # (forwarded only when set: an engine double need not know the keyword)
+                extra = {} if seed is None else {"seed": seed}
+                lp = self._logit_processor_args(sp)
+                extra.update(lp)
+                self.engine.set_sampling_params(b, getattr(sp, "temperature", 0.0) or 0.0, getattr(sp, "top_k", -1) or -1,
+                                                getattr(sp, "top_p", 1.0) if sp is not None else 1.0, **extra)
+                # recomputation: prompt + outputs come back as one token list; penalties and min_tokens tell them apart
+                # (nothing else does: a request without them is admitted exactly as before)
+                npts.append(len(data.get_prompt_token_ids()) if lp and data.get_output_len() else None)
+            if any(n is not None for n in npts):   # (only then: an engine double need not know the keyword)
+                self.engine.add_sequences_to(slots, toks, tables, num_prompt_tokens=npts)
+            else:
+                self.engine.add_sequences_to(slots, toks, tables)
         except Exception:
             for b in slots:
                 self.engine.free_slot(b)
@@ -565,6 +580,30 @@ class SpecDecodeWorker:
             self._slots[s.request_id] = slot
             self._request_id_seq_id_mapping[s.request_id].add(self._only_seq(s)[0])
         return slots
+
+    @staticmethod
+    def _logit_processor_args(sp) -> Dict[str, Any]:
+        """The min_p / penalty / min_tokens keywords of engine.set_sampling_params for a request, EMPTY when every field has
+        its default (as `seed`: such a request makes exactly the calls it always made).  The stop ids of min_tokens are
+        `all_stop_token_ids` where the object has it (a vLLM SamplingParams: stop_token_ids + the EOS id), else
+        `stop_token_ids`; they are forwarded only with a min_tokens > 0, the one thing that reads them."""
+        if sp is None:
+            return {}
+        out: Dict[str, Any] = {}
+        for name, default in (("min_p", 0.0), ("presence_penalty", 0.0), ("frequency_penalty", 0.0),
+                              ("repetition_penalty", 1.0), ("min_tokens", 0)):
+            v = getattr(sp, name, None)
+            if v is not None and v != default:
+                out[name] = v
+        if out.get("min_tokens", 0) > 0:
+            stop = getattr(sp, "all_stop_token_ids", None)
+            if stop is None:
+                stop = getattr(sp, "stop_token_ids", None)
+            stop = sorted(set(int(t) for t in (stop or ())))
+            if len(stop) > 16:
+                raise ValueError(f"min_tokens with {len(stop)} stop token ids: at most 16 are supported")
+            out["stop_token_ids"] = tuple(stop)
+        return out
 
     def _decode_slots(self, sgml) -> List[int]:
         """Engine slots of a decode batch in request order; refreshes block tables (the engine uploads a table only when

@@ -46,7 +46,15 @@ _op("reshape_and_cache_flash(Tensor key, Tensor value, Tensor(a!) key_cache, Ten
 _op("advance_step_flashattn(int num_seqs, int num_queries, int block_size, Tensor(a!) input_tokens, Tensor sampled_token_ids, "
     "Tensor(b!) input_positions, Tensor(c!) seq_lens, Tensor(d!) slot_mapping, Tensor block_tables) -> ()",
     _none(ops.advance_step_flashattn))
+# Sampler.forward's logit processors (sampler.py:258-266) and the top-k / top-p / min_p sampling front end
+_op("process_logits(Tensor logits, Tensor(a!) out, Tensor tok_table, Tensor repetition, Tensor frequency, Tensor presence, "
+    "Tensor min_tokens, Tensor gen_base, Tensor gen_lens, Tensor stop_ids, Tensor num_stop_ids, Tensor? draft_ids=None, "
+    "int rows_per_seq=1, int j_base=0, Tensor? slot_ids=None, Tensor? active_lens=None) -> Tensor(a!)", ops.process_logits)
+_op("logit_table_set_prompt(Tensor(a!) tok_table, Tensor(b!) counted_len, int slot, Tensor prompt_ids, "
+    "Tensor? output_ids=None) -> ()", _none(ops.logit_table_set_prompt))
+_op("logit_table_catch_up(Tensor(a!) tok_table, Tensor(b!) counted_len, Tensor need_counts, Tensor gen_tokens, "
+    "Tensor gen_lens) -> ()", _none(ops.logit_table_catch_up))
 
 OPS = ("rms_norm_general_fuse_sum_i4", "rms_norm_general_fuse_sum_fp16", "fuse_sym_quant", "faster_fast_hadamard_transform",
        "fast_hadamard_transform", "rowwise_scaled_linear_cutlass_s4s4_unified", "w4a16_matmul", "rotary_embedding",
-       "reshape_and_cache_flash", "advance_step_flashattn")
+       "reshape_and_cache_flash", "advance_step_flashattn", "process_logits", "logit_table_set_prompt", "logit_table_catch_up")
