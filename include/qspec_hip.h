@@ -495,6 +495,54 @@ int qspec_sample_top_k_top_p_min_p_seeded(const qspec_half* logits, const float*
                                           const int32_t* seq_seeded, const int32_t* base_pos, int num_seqs, int rows_per_seq,
                                           int j_base, int draw_stream, void* workspace, void* stream);
 
+/* Token constraints: logit_bias, allowed_token_ids and bad words.  The reference's engine lowers them to logits processors
+ *   (vllm/engine/llm_engine.py:1950-2009): logit_bias_logits_processor and AllowedTokenIdsLogitsProcessor
+ *   (vllm/entrypoints/openai/logits_processors.py:10-50), NoBadWordsLogitsProcessor (vllm/logits_process.py:48-119), run on the
+ *   fp16 logits row in front of Sampler.forward (vllm/model_executor/layers/logits_processor.py:134-170), in that order.  Here
+ *   they ride in the pre-pass launch, per ROW as everything else: row j sees the request's outputs -- those it had before its
+ *   admission, the committed ones, the in-flight d_1 .. d_j; never the prompt.
+ *   Per-slot device state, read when the call runs:
+ *     deny [num_slots, deny_words] uint32, deny_words >= ceil(vocab / 32): bit v set = token v is outside allowed_token_ids or
+ *       is a single-token bad word;
+ *     meta [num_slots, 4] int32: {flags (bit 0: the deny row is in use, bit 1: the request has bad words), number of biases,
+ *       number of multi-token bad words, number of tail tokens}.  All zero: the slot is unconstrained and its rows get the
+ *       bits of qspec_process_logits;
+ *     bias_ids [num_slots, QS_MAX_LOGIT_BIAS] int32 sorted ascending and distinct, bias_vals fp32 beside them;
+ *     words [num_slots, QS_MAX_BAD_WORDS, QS_MAX_BAD_WORD_LEN] int32 and word_lens [num_slots, QS_MAX_BAD_WORDS] (2..8);
+ *     tail [num_slots, QS_MAX_BAD_WORD_LEN - 1] int32, RIGHT-aligned: the last outputs the request had before its admission
+ *       (a re-admitted request's gen_tokens start empty), meta[3] of them valid.
+ *   qspec_process_logits_constrained: qspec_process_logits with, in front of its steps, per element
+ *       x[id] = fp16(fp32(x[id]) + bias)                       (an fp16 tensor element += a Python float, as the reference);
+ *       x[v] = -inf where the deny bit of v is set;
+ *       x[w[L-1]] = -inf for every word w of length L whose first L-1 tokens are the last L-1 of outputs + in-flight;
+ *       x = fp16(fp32(x) + 0.0f) for every element of a request that has bad words (the reference adds an fp32 zero
+ *         tensor: -0.0 becomes +0.0).
+ *     gen_tokens [num_slots, gen_cap] int64: the outputs committed since admission, gen_lens of them.
+ *     DIFFERS from the reference where it would produce NaN: a banned token whose logit is +inf or NaN is -inf here (the
+ *     reference ADDS -inf), so a row keeps a usable maximum.
+ *   qspec_token_constraints_set (admission, outside the graph): rebuilds the slot's deny row from allowed_ids / banned_ids
+ *     (int64, ids outside [0, vocab) ignored; num_allowed == 0: no allowed set), copies its bias list (already sorted) and
+ *     its multi-token words, writes meta = {flags, num_bias, num_words, 0}.  All counts zero clears the slot's flags. */
+#define QS_MAX_LOGIT_BIAS 512
+#define QS_MAX_BAD_WORDS 32
+#define QS_MAX_BAD_WORD_LEN 8
+int qspec_process_logits_constrained(const qspec_half* logits, qspec_half* out, int tokens, int vocab, const uint32_t* tok_table,
+                                     int num_slots, const int32_t* slot_ids, const int32_t* active_lens,
+                                     const qspec_half* repetition, const qspec_half* frequency, const qspec_half* presence,
+                                     const int32_t* min_tokens, const int32_t* gen_base, const int32_t* gen_lens,
+                                     const int32_t* stop_ids, const int32_t* num_stop_ids, int stop_ids_per_slot,
+                                     const int64_t* draft_ids, int draft_rows, int64_t ids_stride_b, int64_t ids_stride_k,
+                                     int rows_per_seq, int j_base, const uint32_t* deny, int deny_words, const int32_t* meta,
+                                     const int32_t* bias_ids, const float* bias_vals, const int32_t* words,
+                                     const int32_t* word_lens, const int32_t* tail, const int64_t* gen_tokens, int gen_cap,
+                                     void* stream);
+int qspec_token_constraints_set(uint32_t* deny, int deny_words, int32_t* meta, int32_t* bias_ids, float* bias_vals,
+                                int32_t* words, int32_t* word_lens, int num_slots, int vocab, int slot,
+                                const int64_t* allowed_ids, int num_allowed, const int64_t* banned_ids, int num_banned,
+                                const int32_t* src_bias_ids, const float* src_bias_vals, int num_bias,
+                                const int32_t* src_words, const int32_t* src_word_lens, int num_words, int bad_words_present,
+                                void* stream);
+
 /* TypicalAcceptanceSampler.forward(target_with_bonus_probs, bonus_token_ids, draft_probs, draft_token_ids)
  *   vllm/model_executor/layers/typical_acceptance_sampler.py:37-172 (MEDUSA 3.3.1), selected by
  *   draft_token_acceptance_method = "typical_acceptance_sampler" (vllm/spec_decode/spec_decode_worker.py:95-110).

@@ -103,6 +103,10 @@ SIGNATURES = {
     "qspec_logit_table_catch_up": (_i, [_vp, _vp, _vp, _i, _i, _vp, _i, _vp, _vp]),
     "qspec_process_logits": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i64,
                                   _i64, _i, _i, _vp]),
+    "qspec_process_logits_constrained": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                              _i, _i64, _i64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "qspec_token_constraints_set": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp,
+                                         _i, _i, _vp]),
     "qspec_typical_acceptance_sample": (_i, [_vp, _vp, _vp, _f, _f, _i, _i, _i, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qspec_advance_step_flashattn": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "qspec_spec_prepare_draft": (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),

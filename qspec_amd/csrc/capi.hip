@@ -612,6 +612,69 @@ int qspec_process_logits(const qspec_half* logits, qspec_half* out, int tokens, 
                                             draft_rows > 0 ? draft_ids : nullptr, ids_stride_b, ids_stride_k, rows_per_seq,
                                             j_base, num_slots, stop_ids_per_slot, ST));
 }
+// Token constraints (include/qspec_hip.h, "token constraints"): vllm/entrypoints/openai/logits_processors.py:10-50 and
+// vllm/logits_process.py:48-119 inside the pre-pass launch.
+int qspec_process_logits_constrained(const qspec_half* logits, qspec_half* out, int tokens, int vocab, const uint32_t* tok_table,
+                         int num_slots, const int32_t* slot_ids, const int32_t* active_lens, const qspec_half* repetition,
+                         const qspec_half* frequency, const qspec_half* presence, const int32_t* min_tokens,
+                         const int32_t* gen_base, const int32_t* gen_lens, const int32_t* stop_ids, const int32_t* num_stop_ids,
+                         int stop_ids_per_slot, const int64_t* draft_ids, int draft_rows, int64_t ids_stride_b,
+                         int64_t ids_stride_k, int rows_per_seq, int j_base, const uint32_t* deny, int deny_words, const int32_t* meta,
+                                     const int32_t* bias_ids, const float* bias_vals, const int32_t* words,
+                                     const int32_t* word_lens, const int32_t* tail, const int64_t* gen_tokens, int gen_cap,
+                                     void* stream) {
+    const char* op = "qspec_process_logits_constrained";
+    if (tokens < 0) return fail("%s: tokens < 0", op);
+    if (tokens == 0) return 0;
+    NONNULL(op, logits); NONNULL(op, out); NONNULL(op, tok_table); NONNULL(op, repetition); NONNULL(op, frequency);
+    NONNULL(op, presence); NONNULL(op, min_tokens); NONNULL(op, gen_base); NONNULL(op, gen_lens); NONNULL(op, stop_ids);
+    NONNULL(op, num_stop_ids);
+    NONNULL(op, deny); NONNULL(op, meta); NONNULL(op, bias_ids); NONNULL(op, bias_vals); NONNULL(op, words);
+    NONNULL(op, word_lens); NONNULL(op, tail); NONNULL(op, gen_tokens);
+    if ((int64_t)deny_words * 32 < vocab) return fail("%s: deny_words=%d does not cover vocab=%d", op, deny_words, vocab);
+    if (gen_cap < 1) return fail("%s: gen_cap=%d must be >= 1", op, gen_cap);
+    if (logits == out) return fail("%s: the pass is out of place (logits == out)", op);
+    if (vocab < 1) return fail("%s: vocab < 1", op);
+    if (num_slots < 1) return fail("%s: num_slots=%d must be >= 1", op, num_slots);
+    if (rows_per_seq < 1) return fail("%s: rows_per_seq=%d must be >= 1", op, rows_per_seq);
+    if (j_base < 0) return fail("%s: j_base < 0", op);
+    if (stop_ids_per_slot < 0 || stop_ids_per_slot > QS_MAX_STOP_IDS)
+        return fail("%s: stop_ids_per_slot=%d outside 0..%d", op, stop_ids_per_slot, QS_MAX_STOP_IDS);
+    if (draft_rows < 0 || (draft_rows > 0 && !draft_ids)) return fail("%s: draft_rows=%d without draft_ids", op, draft_rows);
+    if (j_base + rows_per_seq - 1 > draft_rows)
+        return fail("%s: row j=%d needs %d in-flight tokens, draft_ids has %d rows", op, j_base + rows_per_seq - 1,
+                    j_base + rows_per_seq - 1, draft_rows);
+    if (j_base + rows_per_seq - 1 > 64) return fail("%s: more than 64 in-flight tokens", op);
+    if (!slot_ids && (int64_t)num_slots * rows_per_seq < tokens)
+        return fail("%s: num_slots=%d x rows_per_seq=%d does not cover tokens=%d", op, num_slots, rows_per_seq, tokens);
+    return finish(op, qspec::process_logits_constrained(CH(logits), H(out), tokens, vocab, tok_table, slot_ids, active_lens, CH(repetition),
+                                            CH(frequency), CH(presence), min_tokens, gen_base, gen_lens, stop_ids, num_stop_ids,
+                                            draft_rows > 0 ? draft_ids : nullptr, ids_stride_b, ids_stride_k, rows_per_seq,
+                                            j_base, num_slots, stop_ids_per_slot, deny, deny_words, meta, bias_ids,
+                                            bias_vals, words, word_lens, tail, gen_tokens, gen_cap, ST));
+}
+int qspec_token_constraints_set(uint32_t* deny, int deny_words, int32_t* meta, int32_t* bias_ids, float* bias_vals,
+                                int32_t* words, int32_t* word_lens, int num_slots, int vocab, int slot,
+                                const int64_t* allowed_ids, int num_allowed, const int64_t* banned_ids, int num_banned,
+                                const int32_t* src_bias_ids, const float* src_bias_vals, int num_bias,
+                                const int32_t* src_words, const int32_t* src_word_lens, int num_words, int bad_words_present,
+                                void* stream) {
+    const char* op = "qspec_token_constraints_set";
+    NONNULL(op, deny); NONNULL(op, meta); NONNULL(op, bias_ids); NONNULL(op, bias_vals); NONNULL(op, words); NONNULL(op, word_lens);
+    if (vocab < 1) return fail("%s: vocab < 1", op);
+    if ((int64_t)deny_words * 32 < vocab) return fail("%s: deny_words=%d does not cover vocab=%d", op, deny_words, vocab);
+    if (slot < 0 || slot >= num_slots) return fail("%s: slot=%d outside the %d slots", op, slot, num_slots);
+    if (num_allowed < 0 || num_banned < 0) return fail("%s: negative id count", op);
+    if (num_bias < 0 || num_bias > QS_MAX_LOGIT_BIAS) return fail("%s: num_bias=%d outside 0..%d", op, num_bias, QS_MAX_LOGIT_BIAS);
+    if (num_words < 0 || num_words > QS_MAX_BAD_WORDS) return fail("%s: num_words=%d outside 0..%d", op, num_words, QS_MAX_BAD_WORDS);
+    if (num_allowed > 0) NONNULL(op, allowed_ids);
+    if (num_banned > 0) NONNULL(op, banned_ids);
+    if (num_bias > 0) { NONNULL(op, src_bias_ids); NONNULL(op, src_bias_vals); }
+    if (num_words > 0) { NONNULL(op, src_words); NONNULL(op, src_word_lens); }
+    return finish(op, qspec::token_constraints_set(deny, deny_words, meta, bias_ids, bias_vals, words, word_lens, vocab, slot,
+                                                   allowed_ids, num_allowed, banned_ids, num_banned, src_bias_ids, src_bias_vals,
+                                                   num_bias, src_words, src_word_lens, num_words, bad_words_present, ST));
+}
 int qspec_typical_acceptance_sample(const float* target_with_bonus_probs, const int64_t* bonus_token_ids,
                                     const int64_t* draft_token_ids, float posterior_threshold, float posterior_alpha, int batch,
                                     int k, int vocab, int64_t ids_stride_b, int64_t ids_stride_k, int64_t bonus_stride,

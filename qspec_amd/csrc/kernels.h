@@ -208,6 +208,20 @@ int process_logits(const f16* logits, f16* out, int T, int V, const uint32_t* ta
                    const int32_t* gen_base, const int32_t* gen_lens, const int32_t* stop_ids, const int32_t* n_stop,
                    const int64_t* draft_ids, int64_t di_sb, int64_t di_sk, int rows_per_seq, int j_base, int nslots,
                    int stop_width, hipStream_t st);
+// token constraints (logit_bias, allowed_token_ids, bad words) in front of the pipeline above, inside the same launch
+int process_logits_constrained(const f16* logits, f16* out, int T, int V, const uint32_t* table, const int32_t* slot_ids,
+                               const int32_t* active_lens, const f16* rep, const f16* freq, const f16* pres,
+                               const int32_t* min_tokens, const int32_t* gen_base, const int32_t* gen_lens,
+                               const int32_t* stop_ids, const int32_t* n_stop, const int64_t* draft_ids, int64_t di_sb,
+                               int64_t di_sk, int rows_per_seq, int j_base, int nslots, int stop_width, const uint32_t* deny,
+                               int deny_words, const int32_t* meta, const int32_t* bias_ids, const float* bias_vals,
+                               const int32_t* words, const int32_t* word_lens, const int32_t* tail, const int64_t* gen_tokens,
+                               int gen_cap, hipStream_t st);
+int token_constraints_set(uint32_t* deny, int deny_words, int32_t* meta, int32_t* bias_ids, float* bias_vals, int32_t* words,
+                          int32_t* word_lens, int V, int slot, const int64_t* allowed, int n_allowed, const int64_t* banned,
+                          int n_banned, const int32_t* src_bias_ids, const float* src_bias_vals, int n_bias,
+                          const int32_t* src_words, const int32_t* src_word_lens, int n_words, int bad_words_present,
+                          hipStream_t st);
 int typical_acceptance_sample(const float* target_probs, const int64_t* draft_ids, const int64_t* bonus_ids,
                               float posterior_threshold, float posterior_alpha, int B, int k, int V, int64_t di_sb,
                               int64_t di_sk, int64_t bonus_stride, int64_t* out_tokens, uint8_t* accepted, int64_t* recovered,

@@ -979,9 +979,42 @@ struct LpArgs {
     int64_t di_sb, di_sk;
     int V, rows_per_seq, j_base, nslots, stop_width;   // stop_width <= QS_LP_MAX_STOP: row width of stop_ids
 };
+// Token constraints (logit_bias, allowed_token_ids, bad words): the reference's engine lowers them to logits processors
+// (vllm/engine/llm_engine.py:1950-2009; vllm/entrypoints/openai/logits_processors.py:10-50; vllm/logits_process.py:48-119) that
+// run on the fp16 row in front of Sampler.forward (vllm/model_executor/layers/logits_processor.py:134-170).  Per-slot state:
+//   deny [nslots, deny_words] u32: bit v = token v is outside allowed_token_ids or is a single-token bad word;
+//   meta [nslots, 4] i32: flags (bit 0: the deny row is in use, bit 1: the request has bad words), number of biases, number of
+//     multi-token bad words, length of the tail;
+//   bias_ids / bias_vals [nslots, 512]: logit_bias, sorted by id;  words [nslots, 32, 8] / word_lens [nslots, 32];
+//   tail [nslots, 7] i32, right-aligned: the last outputs the request had BEFORE its admission (gen_tokens starts empty then).
+#define QS_TC_MAX_BIAS 512     // QS_MAX_LOGIT_BIAS of include/qspec_hip.h
+#define QS_TC_MAX_WORDS 32     // QS_MAX_BAD_WORDS
+#define QS_TC_WORD_LEN 8       // QS_MAX_BAD_WORD_LEN
+struct LpCons {
+    const uint32_t* deny;
+    const int32_t* meta;
+    const int32_t* bias_ids;
+    const float* bias_vals;
+    const int32_t* words;
+    const int32_t* word_lens;
+    const int32_t* tail;
+    const int64_t* gen_tokens;    // [nslots, gen_cap] the outputs committed since admission
+    int gen_cap, deny_words;
+};
+struct LpArgsC : LpArgs { LpCons c; };
+template <bool C> struct LpArgsOf { typedef LpArgs type; };
+template <> struct LpArgsOf<true> { typedef LpArgsC type; };
 // grid (chunks of 2048 logits, rows): 16-byte loads of the logits and of the table words, 16-byte stores; a row is wave-uniform
 // in everything but the element itself.  About 8 B of traffic per element (2 + 4 read, 2 written).
-__global__ __launch_bounds__(256) void process_logits_kernel(LpArgs a) {
+// C (token constraints, in front of the pipeline above): x[id] = fp16(x[id] + bias); deny bits and matched multi-token bad words
+// -> -inf; a request with bad words adds the reference's fp32 zero to every element (-0.0 becomes +0.0).  All -inf assignments
+// commute with a finite bias, so the order among them is free; all of them land before lp_element, whose repetition rule looks
+// at the sign.  One byte of the deny row covers a thread's 8 logits.  Biases and banned last tokens that fall into the
+// workgroup's chunk are applied to the chunk staged in LDS (no workgroup stages anything when none does: __syncthreads_or).
+// Every workgroup of a row resolves the bad-word matches itself: threads 0..6 fetch the row's last 7 tokens (in-flight, then
+// committed, then the pre-admission tail), threads 0..31 compare one word each.  Nothing is written but `out`.
+template <bool C>
+__global__ __launch_bounds__(256) void process_logits_kernel(typename LpArgsOf<C>::type a) {
     __shared__ int64_t s_inflight[QS_LP_MAX_INFLIGHT];
     __shared__ int32_t s_stop[QS_LP_MAX_STOP];
     const int t = blockIdx.y, seq = t / a.rows_per_seq, j = a.j_base + t % a.rows_per_seq;
@@ -1000,9 +1033,117 @@ __global__ __launch_bounds__(256) void process_logits_kernel(LpArgs a) {
     r.n_inflight = (r.table && a.draft_ids) ? min(j, QS_LP_MAX_INFLIGHT) : 0;
     if ((int)threadIdx.x < r.n_inflight) s_inflight[threadIdx.x] = a.draft_ids[slot * a.di_sb + threadIdx.x * a.di_sk];
     if ((int)threadIdx.x < r.n_stop) s_stop[threadIdx.x] = a.stop_ids[slot * a.stop_width + threadIdx.x];
+    const int lo = blockIdx.x * QS_LP_CHUNK, v0 = lo + 8 * (int)threadIdx.x;
+    if constexpr (C) {
+        __shared__ int64_t s_last[QS_TC_WORD_LEN - 1];   // s_last[p - 1]: the p-th token from the end of outputs + in-flight
+        __shared__ f16 s_x[QS_LP_CHUNK];
+        const int tid = threadIdx.x;
+        const int4 meta = *reinterpret_cast<const int4*>(a.c.meta + 4 * slot);
+        const bool deny_on = on && (meta.x & 1), zero_add = on && (meta.x & 2);
+        const int n_bias = on ? min(max(meta.y, 0), QS_TC_MAX_BIAS) : 0;
+        const int n_words = on ? min(max(meta.z, 0), QS_TC_MAX_WORDS) : 0;
+        const bool vec = V % 8 == 0;
+        // the element loads first: everything below overlaps them
+        f16x8 x = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        u32x4 w0 = u32x4{0u, 0u, 0u, 0u}, w1 = w0;
+        const uint32_t* w = a.table + (size_t)slot * V;
+        uint32_t deny = 0u;
+        if (v0 < V) {
+            if (vec) {
+                x = *reinterpret_cast<const f16x8*>(l + v0);
+                if (r.table) {
+                    w0 = *reinterpret_cast<const u32x4*>(w + v0);
+                    w1 = *reinterpret_cast<const u32x4*>(w + v0 + 4);
+                }
+            } else {
+                for (int e = 0; e < 8; e++)
+                    if (v0 + e < V) {
+                        x[e] = l[v0 + e];
+                        const uint32_t we = r.table ? w[v0 + e] : 0u;
+                        if (e < 4) w0[e] = we; else w1[e - 4] = we;
+                    }
+            }
+            deny = reinterpret_cast<const uint8_t*>(a.c.deny + (size_t)slot * a.c.deny_words)[v0 >> 3];
+        }
+        if (!deny_on) deny = 0u;
+        // logit_bias entries of this thread (two at most) that fall into the chunk
+        int bid[2]; float bval[2];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const int i = tid + 256 * e;
+            bid[e] = i < n_bias ? a.c.bias_ids[slot * QS_TC_MAX_BIAS + i] - lo : -1;
+            bval[e] = i < n_bias ? a.c.bias_vals[slot * QS_TC_MAX_BIAS + i] : 0.0f;
+            if (bid[e] < 0 || bid[e] >= QS_LP_CHUNK || bid[e] + lo >= V) bid[e] = -1;
+        }
+        // multi-token bad words: the last 7 tokens of the row's prefix, then one word per thread
+        if (n_words > 0 && tid < QS_TC_WORD_LEN - 1) {
+            const int p = tid + 1;
+            int64_t tok = -1;
+            const int gl = min(max(a.gen_lens[slot], 0), a.c.gen_cap);
+            const int tl = min(max(meta.w, 0), QS_TC_WORD_LEN - 1);
+            if (p <= j) {
+                if (a.draft_ids) tok = a.draft_ids[slot * a.di_sb + (int64_t)(j - p) * a.di_sk];
+            } else if (p - j <= gl) {
+                tok = a.c.gen_tokens[(size_t)slot * a.c.gen_cap + (gl - (p - j))];
+            } else if (p - j - gl <= tl) {
+                tok = a.c.tail[slot * (QS_TC_WORD_LEN - 1) + (QS_TC_WORD_LEN - 1) - (p - j - gl)];
+            }
+            s_last[tid] = tok;
+        }
+        int4 wa = int4{-1, -1, -1, -1}, wb = wa;
+        int wl = 0;
+        if (tid < n_words) {
+            const int32_t* wp = a.c.words + ((size_t)slot * QS_TC_MAX_WORDS + tid) * QS_TC_WORD_LEN;
+            wa = *reinterpret_cast<const int4*>(wp);
+            wb = *reinterpret_cast<const int4*>(wp + 4);
+            wl = min(max(a.c.word_lens[slot * QS_TC_MAX_WORDS + tid], 2), QS_TC_WORD_LEN);
+        }
+        __syncthreads();
+        int ban = -1;
+        if (tid < n_words) {
+            const int ws[QS_TC_WORD_LEN] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+            bool match = true;
+            int last = -1;
+#pragma unroll
+            for (int i = 0; i < QS_TC_WORD_LEN; i++) {
+                if (i < wl - 1) match = match && (int64_t)ws[i] == s_last[wl - 2 - i];
+                if (i == wl - 1) last = ws[i];
+            }
+            if (match && last >= lo && last < lo + QS_LP_CHUNK && last < V) ban = last - lo;
+        }
+        bool staged = false;
+        if (n_bias > 0 || n_words > 0) staged = __syncthreads_or(bid[0] >= 0 || bid[1] >= 0 || ban >= 0);
+        if (staged) {   // (workgroup-uniform)
+            *reinterpret_cast<f16x8*>(s_x + 8 * tid) = x;
+            __syncthreads();
+#pragma unroll
+            for (int e = 0; e < 2; e++)   // ids are distinct: one writer per element
+                if (bid[e] >= 0) s_x[bid[e]] = f2h(h2f(s_x[bid[e]]) + bval[e]);
+            __syncthreads();
+            if (ban >= 0) s_x[ban] = f2h(-__builtin_inff());   // (two words may ban the same token: the same value)
+            __syncthreads();
+            x = *reinterpret_cast<const f16x8*>(s_x + 8 * tid);
+        }
+        if (v0 >= V) return;
+        const bool lp = r.table || r.stop;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            f16 xe = x[e];
+            if ((deny >> e) & 1u) xe = f2h(-__builtin_inff());
+            if (zero_add) xe = f2h(h2f(xe) + 0.0f);
+            if (lp) xe = lp_element(xe, v0 + e, e < 4 ? w0[e] : w1[e - 4], r, s_inflight, s_stop);
+            x[e] = xe;
+        }
+        if (vec) {
+            *reinterpret_cast<f16x8*>(o + v0) = x;
+        } else {
+            for (int e = 0; e < 8; e++)
+                if (v0 + e < V) o[v0 + e] = x[e];
+        }
+        return;
+    }
     __syncthreads();
     const uint32_t* w = a.table + (size_t)slot * V;
-    const int lo = blockIdx.x * QS_LP_CHUNK, v0 = lo + 8 * (int)threadIdx.x;
     if (v0 >= V) return;
     if (V % 8 == 0) {   // rows are 16-byte aligned: one f16x8 per thread (v0 + 8 <= V follows from V % 8 == 0)
         f16x8 x = *reinterpret_cast<const f16x8*>(l + v0);
@@ -1025,16 +1166,88 @@ __global__ __launch_bounds__(256) void process_logits_kernel(LpArgs a) {
         }
     }
 }
+static bool lp_args_ok(int V, int rows_per_seq, int j_base, int nslots, int stop_width) {
+    return !(stop_width < 0 || stop_width > QS_LP_MAX_STOP || nslots < 1 || rows_per_seq < 1 || j_base < 0 ||
+             j_base + rows_per_seq - 1 > QS_LP_MAX_INFLIGHT);
+}
 int process_logits(const f16* logits, f16* out, int T, int V, const uint32_t* table, const int32_t* slot_ids,
                    const int32_t* active_lens, const f16* rep, const f16* freq, const f16* pres, const int32_t* min_tokens,
                    const int32_t* gen_base, const int32_t* gen_lens, const int32_t* stop_ids, const int32_t* n_stop,
                    const int64_t* draft_ids, int64_t di_sb, int64_t di_sk, int rows_per_seq, int j_base, int nslots,
                    int stop_width, hipStream_t st) {
     if (T == 0) return 0;
-    if (stop_width < 0 || stop_width > QS_LP_MAX_STOP || nslots < 1 || rows_per_seq < 1 || j_base < 0 || j_base + rows_per_seq - 1 > QS_LP_MAX_INFLIGHT) return -1;
+    if (!lp_args_ok(V, rows_per_seq, j_base, nslots, stop_width)) return -1;
     LpArgs a{logits, out, table, slot_ids, active_lens, rep, freq, pres, min_tokens, gen_base, gen_lens, stop_ids, n_stop,
              draft_ids, di_sb, di_sk, V, rows_per_seq, j_base, nslots, stop_width};
-    hipLaunchKernelGGL(process_logits_kernel, dim3((V + QS_LP_CHUNK - 1) / QS_LP_CHUNK, T), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(process_logits_kernel<false>, dim3((V + QS_LP_CHUNK - 1) / QS_LP_CHUNK, T), dim3(256), 0, st, a);
+    return 0;
+}
+int process_logits_constrained(const f16* logits, f16* out, int T, int V, const uint32_t* table, const int32_t* slot_ids,
+                               const int32_t* active_lens, const f16* rep, const f16* freq, const f16* pres,
+                               const int32_t* min_tokens, const int32_t* gen_base, const int32_t* gen_lens,
+                               const int32_t* stop_ids, const int32_t* n_stop, const int64_t* draft_ids, int64_t di_sb,
+                               int64_t di_sk, int rows_per_seq, int j_base, int nslots, int stop_width, const uint32_t* deny,
+                               int deny_words, const int32_t* meta, const int32_t* bias_ids, const float* bias_vals,
+                               const int32_t* words, const int32_t* word_lens, const int32_t* tail, const int64_t* gen_tokens,
+                               int gen_cap, hipStream_t st) {
+    if (T == 0) return 0;
+    if (!lp_args_ok(V, rows_per_seq, j_base, nslots, stop_width) || gen_cap < 1 || (int64_t)deny_words * 32 < V) return -1;
+    LpArgsC a;
+    static_cast<LpArgs&>(a) = LpArgs{logits, out, table, slot_ids, active_lens, rep, freq, pres, min_tokens, gen_base, gen_lens,
+                                     stop_ids, n_stop, draft_ids, di_sb, di_sk, V, rows_per_seq, j_base, nslots, stop_width};
+    a.c = LpCons{deny, meta, bias_ids, bias_vals, words, word_lens, tail, gen_tokens, gen_cap, deny_words};
+    hipLaunchKernelGGL(process_logits_kernel<true>, dim3((V + QS_LP_CHUNK - 1) / QS_LP_CHUNK, T), dim3(256), 0, st, a);
+    return 0;
+}
+// Admission (outside the graph): ONE workgroup builds the slot's deny row -- all ones where the request has allowed_token_ids,
+// their bits cleared, the single-token bad words' bits set (integer atomics: the result does not depend on the order) -- and
+// copies its sorted bias list and its multi-token bad words.  meta = {flags, n_bias, n_words, 0}: the tail is the admission's.
+// Ids outside [0, V) are ignored.  Everything zero: the slot is unconstrained (the row is left alone, its flag says unused).
+__global__ __launch_bounds__(1024) void token_constraints_set_kernel(
+    uint32_t* __restrict__ deny, int deny_words, int V, const int64_t* __restrict__ allowed, int n_allowed,
+    const int64_t* __restrict__ banned, int n_banned, int32_t* __restrict__ bias_ids, float* __restrict__ bias_vals,
+    const int32_t* __restrict__ src_bias_ids, const float* __restrict__ src_bias_vals, int n_bias, int32_t* __restrict__ words,
+    int32_t* __restrict__ word_lens, const int32_t* __restrict__ src_words, const int32_t* __restrict__ src_word_lens,
+    int n_words, int32_t* __restrict__ meta, int bad_words_present) {
+    const int tid = threadIdx.x;
+    if (n_allowed > 0 || n_banned > 0) {
+        const uint32_t fill = n_allowed > 0 ? 0xFFFFFFFFu : 0u;
+        for (int i = tid; i < deny_words; i += blockDim.x) deny[i] = fill;
+        __syncthreads();
+        for (int i = tid; i < n_allowed; i += blockDim.x) {
+            const int64_t v = allowed[i];
+            if (v >= 0 && v < V) atomicAnd(deny + (v >> 5), ~(1u << (v & 31)));
+        }
+        __syncthreads();
+        for (int i = tid; i < n_banned; i += blockDim.x) {
+            const int64_t v = banned[i];
+            if (v >= 0 && v < V) atomicOr(deny + (v >> 5), 1u << (v & 31));
+        }
+    }
+    for (int i = tid; i < n_bias; i += blockDim.x) {
+        bias_ids[i] = src_bias_ids[i];
+        bias_vals[i] = src_bias_vals[i];
+    }
+    for (int i = tid; i < n_words * QS_TC_WORD_LEN; i += blockDim.x) words[i] = src_words[i];
+    for (int i = tid; i < n_words; i += blockDim.x) word_lens[i] = src_word_lens[i];
+    if (tid == 0) {
+        meta[0] = ((n_allowed > 0 || n_banned > 0) ? 1 : 0) | (bad_words_present ? 2 : 0);
+        meta[1] = n_bias;
+        meta[2] = n_words;
+        meta[3] = 0;
+    }
+}
+int token_constraints_set(uint32_t* deny, int deny_words, int32_t* meta, int32_t* bias_ids, float* bias_vals, int32_t* words,
+                          int32_t* word_lens, int V, int slot, const int64_t* allowed, int n_allowed, const int64_t* banned,
+                          int n_banned, const int32_t* src_bias_ids, const float* src_bias_vals, int n_bias,
+                          const int32_t* src_words, const int32_t* src_word_lens, int n_words, int bad_words_present,
+                          hipStream_t st) {
+    if (n_bias > QS_TC_MAX_BIAS || n_words > QS_TC_MAX_WORDS || (int64_t)deny_words * 32 < V) return -1;
+    hipLaunchKernelGGL(token_constraints_set_kernel, dim3(1), dim3(1024), 0, st, deny + (size_t)slot * deny_words, deny_words, V,
+                       allowed, n_allowed, banned, n_banned, bias_ids + (size_t)slot * QS_TC_MAX_BIAS,
+                       bias_vals + (size_t)slot * QS_TC_MAX_BIAS, src_bias_ids, src_bias_vals, n_bias,
+                       words + (size_t)slot * QS_TC_MAX_WORDS * QS_TC_WORD_LEN, word_lens + (size_t)slot * QS_TC_MAX_WORDS,
+                       src_words, src_word_lens, n_words, meta + 4 * slot, bad_words_present);
     return 0;
 }
 

@@ -832,6 +832,120 @@ def process_logits(logits, out, tok_table, repetition, frequency, presence, min_
     return out
 
 
+# ------------------------------------------------------------------ token constraints (include/qspec_hip.h, "token constraints")
+MAX_LOGIT_BIAS = 512     # QS_MAX_LOGIT_BIAS
+MAX_BAD_WORDS = 32       # QS_MAX_BAD_WORDS (multi-token words; single-token ones live in the deny bitmask)
+MAX_BAD_WORD_LEN = 8     # QS_MAX_BAD_WORD_LEN
+
+
+class TokenConstraints:
+    """The per-slot device arrays of logit_bias / allowed_token_ids / bad words (all zero: no slot is constrained)."""
+
+    def __init__(self, num_slots: int, vocab: int, device):
+        z = lambda *shape, dtype=_I32: torch.zeros(*shape, dtype=dtype, device=device)   # noqa: E731
+        self.num_slots, self.vocab = num_slots, vocab
+        self.deny = z(num_slots, (vocab + 31) // 32)          # bit v: not allowed, or a single-token bad word
+        self.meta = z(num_slots, 4)                           # flags, biases, multi-token words, tail tokens
+        self.bias_ids = z(num_slots, MAX_LOGIT_BIAS)
+        self.bias_vals = z(num_slots, MAX_LOGIT_BIAS, dtype=_F32)
+        self.words = z(num_slots, MAX_BAD_WORDS, MAX_BAD_WORD_LEN)
+        self.word_lens = z(num_slots, MAX_BAD_WORDS)
+        self.tail = z(num_slots, MAX_BAD_WORD_LEN - 1)        # right-aligned: the outputs a request had before admission
+
+    def arrays(self):
+        return (self.deny, self.meta, self.bias_ids, self.bias_vals, self.words, self.word_lens, self.tail)
+
+
+def token_constraints_set(tc: TokenConstraints, slot: int, logit_bias=None, allowed_token_ids=None, bad_words_token_ids=None):
+    """Rebuild the constraint state of `slot` (admission time, outside any graph).  logit_bias: {id: bias} (ids distinct),
+    allowed_token_ids: ids or None, bad_words_token_ids: lists of ids -- validated by the caller (the engine); here only the
+    caps are enforced.  All None / empty: the slot's flags are cleared.  The tail (meta[3]) is reset to 0."""
+    dev = tc.deny.device
+    bias = sorted((int(t), float(b)) for t, b in (logit_bias or {}).items())
+    allowed = sorted(set(int(t) for t in allowed_token_ids)) if allowed_token_ids is not None else []
+    words = [[int(t) for t in w] for w in (bad_words_token_ids or [])]
+    single = sorted(set(w[0] for w in words if len(w) == 1))
+    multi = []
+    for w in words:
+        if len(w) > 1 and w not in multi:
+            multi.append(w)
+    if len(bias) > MAX_LOGIT_BIAS:
+        raise ValueError(f"{len(bias)} logit_bias entries: at most {MAX_LOGIT_BIAS} are supported")
+    if len(multi) > MAX_BAD_WORDS:
+        raise ValueError(f"{len(multi)} multi-token bad words: at most {MAX_BAD_WORDS} are supported")
+    if any(len(w) > MAX_BAD_WORD_LEN for w in multi):
+        raise ValueError(f"a bad word is longer than {MAX_BAD_WORD_LEN} tokens")
+
+    def dev_t(vals, dtype):
+        return torch.tensor(vals, dtype=dtype).to(dev) if len(vals) else None
+    a_t, s_t = dev_t(allowed, _I64), dev_t(single, _I64)
+    bi_t, bv_t = dev_t([t for t, _ in bias], _I32), dev_t([b for _, b in bias], _F32)
+    w_t = dev_t([w + [-1] * (MAX_BAD_WORD_LEN - len(w)) for w in multi], _I32)
+    wl_t = dev_t([len(w) for w in multi], _I32)
+    ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    _call("qspec_token_constraints_set", _chk(tc.deny, "deny", _I32), tc.deny.shape[1], _chk(tc.meta, "meta", _I32),
+          _chk(tc.bias_ids, "bias_ids", _I32), _chk(tc.bias_vals, "bias_vals", _F32), _chk(tc.words, "words", _I32),
+          _chk(tc.word_lens, "word_lens", _I32), tc.num_slots, tc.vocab, int(slot), ptr(a_t), len(allowed), ptr(s_t), len(single),
+          ptr(bi_t), ptr(bv_t), len(bias), ptr(w_t), ptr(wl_t), len(multi), int(bool(words)), _stream())
+    # (the staging tensors are freed behind the launch: the caching allocator reuses memory in stream order)
+
+
+def token_constraints_set_tail(tc: TokenConstraints, slot: int, outputs_before_admission) -> None:
+    """The last MAX_BAD_WORD_LEN - 1 outputs a re-admitted request had before its admission (right-aligned) and their number."""
+    n = MAX_BAD_WORD_LEN - 1
+    last = [int(t) for t in list(outputs_before_admission)[-n:]]
+    tc.tail[slot].copy_(torch.tensor([-1] * (n - len(last)) + last, dtype=_I32))
+    tc.meta[slot, 3] = len(last)
+
+
+def process_logits_constrained(logits, out, tok_table, repetition, frequency, presence, min_tokens, gen_base, gen_lens, stop_ids,
+                               num_stop_ids, deny, meta, bias_ids, bias_vals, words, word_lens, tail, gen_tokens,
+                               draft_ids=None, rows_per_seq: int = 1, j_base: int = 0, slot_ids=None, active_lens=None):
+    """process_logits with the token constraints in front of it, in the same launch: logit_bias, the deny bitmask (tokens outside
+    allowed_token_ids, single-token bad words) and the multi-token bad words matched against the request's outputs -- the tail
+    it had before admission, gen_tokens[slot][:gen_lens], the in-flight draft_ids[0 .. j, slot].  The arrays are those of a
+    TokenConstraints; a slot whose meta row is zero gets the bits of process_logits."""
+    T, V = logits.shape
+    B = tok_table.shape[0]
+    if tok_table.shape[1] != V or out.shape != logits.shape:
+        raise RuntimeError("tok_table / out do not match the logits")
+    for t, name in ((repetition, "repetition"), (frequency, "frequency"), (presence, "presence"), (min_tokens, "min_tokens"),
+                    (gen_base, "gen_base"), (gen_lens, "gen_lens"), (num_stop_ids, "num_stop_ids")):
+        if t.numel() < B:
+            raise RuntimeError(f"{name} has {t.numel()} entries, the table has {B} slots")
+    if stop_ids.dim() != 2 or stop_ids.shape[0] < B:
+        raise RuntimeError("stop_ids must be [num_slots, width]")
+    if deny.dim() != 2 or deny.shape[0] < B or deny.shape[1] * 32 < V:
+        raise RuntimeError("deny must be [num_slots, >= ceil(vocab / 32)]")
+    for t, shape, name in ((meta, (4,), "meta"), (bias_ids, (MAX_LOGIT_BIAS,), "bias_ids"), (bias_vals, (MAX_LOGIT_BIAS,), "bias_vals"),
+                           (words, (MAX_BAD_WORDS, MAX_BAD_WORD_LEN), "words"), (word_lens, (MAX_BAD_WORDS,), "word_lens"),
+                           (tail, (MAX_BAD_WORD_LEN - 1,), "tail")):
+        if t.shape[0] < B or tuple(t.shape[1:]) != shape:
+            raise RuntimeError(f"{name} must be [num_slots, {', '.join(str(d) for d in shape)}]")
+    if gen_tokens.dim() != 2 or gen_tokens.shape[0] < B:
+        raise RuntimeError("gen_tokens must be [num_slots, capacity]")
+    nseq = (T + rows_per_seq - 1) // max(1, rows_per_seq)
+    if slot_ids is not None and slot_ids.numel() < nseq:
+        raise RuntimeError(f"slot_ids has {slot_ids.numel()} entries, {nseq} sequences need one each")
+    if active_lens is not None and active_lens.numel() < B:
+        raise RuntimeError("active_lens is shorter than the table")
+    n_draft, di_sb, di_sk, di_ptr = 0, 0, 0, None
+    if draft_ids is not None:
+        if draft_ids.dim() != 2 or draft_ids.shape[1] < B or draft_ids.dtype != _I64 or not draft_ids.is_cuda:
+            raise RuntimeError("draft_ids must be an int64 [steps, num_slots] GPU tensor")
+        n_draft, di_sk, di_sb, di_ptr = draft_ids.shape[0], draft_ids.stride(0), draft_ids.stride(1), draft_ids.data_ptr()
+    _call("qspec_process_logits_constrained", _chk(logits, "logits", _F16), _chk(out, "out", _F16), T, V,
+          _chk(tok_table, "tok_table", _I32), B, _opt(slot_ids, "slot_ids", _I32), _opt(active_lens, "active_lens", _I32),
+          _chk(repetition, "repetition", _F16), _chk(frequency, "frequency", _F16), _chk(presence, "presence", _F16),
+          _chk(min_tokens, "min_tokens", _I32), _chk(gen_base, "gen_base", _I32), _chk(gen_lens, "gen_lens", _I32),
+          _chk(stop_ids, "stop_ids", _I32), _chk(num_stop_ids, "num_stop_ids", _I32), stop_ids.shape[1], di_ptr, n_draft, di_sb,
+          di_sk, rows_per_seq, j_base, _chk(deny, "deny", _I32), deny.shape[1], _chk(meta, "meta", _I32),
+          _chk(bias_ids, "bias_ids", _I32), _chk(bias_vals, "bias_vals", _F32), _chk(words, "words", _I32),
+          _chk(word_lens, "word_lens", _I32), _chk(tail, "tail", _I32), _chk(gen_tokens, "gen_tokens", _I64),
+          gen_tokens.shape[1], _stream())
+    return out
+
+
 def typical_acceptance_sample(target_with_bonus_probs, bonus_token_ids, draft_token_ids, posterior_threshold: float,
                               posterior_alpha: float, out_tokens, accepted, recovered, counters=None, workspace=None,
                               active_lens=None):

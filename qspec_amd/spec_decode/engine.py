@@ -186,6 +186,16 @@ class QSpecEngine:
         self._mode_processing = False
         self._graph_p: Optional[torch.cuda.CUDAGraph] = None       # the sampling cycle with the logit processors
         self._graph_draft_p: Optional[torch.cuda.CUDAGraph] = None
+        # ---- token constraints per slot: logit_bias, allowed_token_ids, bad words (what the reference's engine lowers to logits
+        # processors in front of Sampler.forward; include/qspec_hip.h, "token constraints").  Device arrays (ops.TokenConstraints:
+        # a deny bitmask, a sorted bias list, the multi-token words, the pre-admission tail) allocated on first use and read at
+        # replay.  While an occupied slot carries one, the engine replays a FOURTH captured cycle: the processed cycle with the
+        # constrained pre-pass entry in place of the plain one (same launches).  Every other batch replays what it always did.
+        self._tc_host = None                                       # per slot None, or (biases, allowed ids, bad words)
+        self.tc = None
+        self._mode_constrained = False
+        self._graph_c: Optional[torch.cuda.CUDAGraph] = None       # the processed cycle with the token constraints
+        self._graph_draft_c: Optional[torch.cuda.CUDAGraph] = None
         # test hooks: injected random draws for the rejection sampler (eager mode only)
         self.inject_uniform: Optional[torch.Tensor] = None
         self.inject_exponential: Optional[torch.Tensor] = None
@@ -195,9 +205,17 @@ class QSpecEngine:
     _lp_host: Optional[list] = None             # None until a request first uses a logit processor
     tok_table: Optional[torch.Tensor] = None
     _mode_processing = False
+    _tc_host: Optional[list] = None             # None until a request first carries a token constraint
+    tc = None
+    _mode_constrained = False
+    _graph_c = None
+    _graph_draft_c = None
 
     def _lp(self, slot: int):
         return self._LP_NEUTRAL if self._lp_host is None else self._lp_host[slot]
+
+    def _tc(self, slot: int):
+        return None if self._tc_host is None else self._tc_host[slot]
 
     # the embedding lookups of the cycle's four forwards ride in the bookkeeping launches in front of them (5 launches less)
     EMBED_IN_BOOKKEEPING = os.environ.get("QSPEC_EMBED_IN_BOOKKEEPING", "1") != "0"
@@ -337,10 +355,11 @@ class QSpecEngine:
     def _first_token(self, logits, probs, tok, slots: List[int], prompt_lens: List[int]) -> None:
         """The target's first token of freshly admitted prompts: greedy, or sampled with the slots' parameters (a seeded
         request: target stream, j = 0, base position = its prompt length)."""
-        processed = any(self._lp(b) != self._LP_NEUTRAL for b in slots)
+        constrained = any(self._tc(b) is not None for b in slots)
+        processed = constrained or any(self._lp(b) != self._LP_NEUTRAL for b in slots)
         if processed:   # position 0 of the request: j = 0, no in-flight tokens (gen_lens of a fresh slot is 0)
             logits = self._process(logits, torch.empty_like(logits), rows_per_seq=1, j_base=0, draft_ids=None, active_lens=None,
-                                   slot_ids=torch.tensor(slots, dtype=torch.int32, device=self.device))
+                                   slot_ids=torch.tensor(slots, dtype=torch.int32, device=self.device), constrained=constrained)
         if all(self._samp_host[b][0] < 1e-5 for b in slots):
             ops.softmax_argmax(logits, probs, tok)
             return
@@ -376,7 +395,8 @@ class QSpecEngine:
     def set_sampling_params(self, slot: int, temperature: float = 0.0, top_k: int = -1, top_p: float = 1.0,
                             seed: Optional[int] = None, min_p: float = 0.0, presence_penalty: float = 0.0,
                             frequency_penalty: float = 0.0, repetition_penalty: float = 1.0, min_tokens: int = 0,
-                            stop_token_ids: Sequence[int] = ()) -> None:
+                            stop_token_ids: Sequence[int] = (), logit_bias=None, allowed_token_ids=None,
+                            bad_words_token_ids=None) -> None:
         """The request in `slot` samples with these parameters (vllm/sampling_params.py; temperature < 1e-5 = greedy, for
         which vLLM itself resets top_k / top_p).  seed (SamplingParams.seed, taken mod 2^64): the request's draws depend
         on it and its own positions only; a greedy request makes no draws and ignores it.  Uploaded only when they
@@ -385,7 +405,14 @@ class QSpecEngine:
         not be emitted before min_tokens tokens were generated, the EOS id included): vllm/sampling_params.py; applied per row
         of the cycle as the non-speculative sampler would apply them at that position.  They belong to the request: set them
         BEFORE its admission (the admission builds the slot's token table).  Refused with ValueError, nothing enqueued: more
-        than 16 stop ids, min_p outside [0, 1], repetition_penalty <= 0, min_tokens < 0, non-finite penalties."""
+        than 16 stop ids, min_p outside [0, 1], repetition_penalty <= 0, min_tokens < 0, non-finite penalties.
+        logit_bias ({id: bias}, taken as given: the reference clamps to [-100, 100] where it lowers the request, not here),
+        allowed_token_ids, bad_words_token_ids (lists of token ids; single-token words are unlimited, at most 32 longer ones
+        of at most 8 tokens, at most 512 biases): hard constraints applied in front of everything above, per row, the bad
+        words matched against the request's OUTPUTS (in flight included), never its prompt.  Like the penalties they are set
+        BEFORE admission.  Refused with ValueError, nothing enqueued: an id outside the vocabulary, an empty allowed set or
+        bad word, a cap exceeded, a non-finite bias, an occupied slot, and a request that can never emit anything (every
+        allowed token is a single-token bad word -- or, with min_tokens, a stop id)."""
         stop = tuple(int(t) for t in stop_token_ids)
         vals = (float(min_p), float(presence_penalty), float(frequency_penalty), float(repetition_penalty))
         if len(stop) > ops.MAX_STOP_IDS:
@@ -398,6 +425,8 @@ class QSpecEngine:
             raise ValueError(f"repetition_penalty {repetition_penalty} must be > 0")
         if int(min_tokens) < 0:
             raise ValueError(f"min_tokens {min_tokens} must be >= 0")
+        want_tc = self._validate_constraints(slot, logit_bias, allowed_token_ids, bad_words_token_ids,
+                                             stop if int(min_tokens) > 0 else ())
         if temperature < 1e-5:   # (min_p is reset for greedy requests, sampling_params.py:344; the rest applies to them too)
             temperature, top_k, top_p, seed = 0.0, -1, 1.0, None
             vals = (0.0,) + vals[1:]
@@ -425,6 +454,14 @@ class QSpecEngine:
             self.lp_n_stop[slot] = len(stop)
             self.lp_need[slot] = need
             self._lp_host[slot] = want_lp
+        if want_tc != self._tc(slot):
+            self._ensure_processing()
+            self._ensure_constraints()
+            if want_tc is None:
+                ops.token_constraints_set(self.tc, slot)           # flags off: the slot is unconstrained again
+            else:
+                ops.token_constraints_set(self.tc, slot, dict(want_tc[0]), want_tc[1], [list(w) for w in want_tc[2]])
+            self._tc_host[slot] = want_tc
         want_seed = None if seed is None else int(seed) % (1 << 64)
         if self._seed_host[slot] != want_seed:
             self.seq_seed[slot] = 0 if want_seed is None else want_seed - (1 << 64) * (want_seed >= 1 << 63)
@@ -440,13 +477,70 @@ class QSpecEngine:
         self.v_samp_topp[slot * k1:(slot + 1) * k1] = want[2]
         self._samp_host[slot] = want
 
+    def _validate_constraints(self, slot: int, logit_bias, allowed_token_ids, bad_words_token_ids, stop: Sequence[int]):
+        """The canonical form of a request's token constraints -- (sorted (id, bias) pairs, sorted allowed ids or None, bad
+        words) -- or None when it has none.  Raises ValueError; enqueues nothing."""
+        if not logit_bias and allowed_token_ids is None and not bad_words_token_ids:
+            return None
+        V = self.cfg.vocab_size
+        try:
+            bias = {int(t): float(b) for t, b in (logit_bias or {}).items()}
+        except (TypeError, ValueError) as exc:
+            raise ValueError("logit_bias maps token ids (integers or strings of integers) to numbers") from exc
+        allowed = None if allowed_token_ids is None else tuple(sorted(set(int(t) for t in allowed_token_ids)))
+        words = []
+        for w in (bad_words_token_ids or ()):
+            w = tuple(int(t) for t in w)
+            if not w:
+                raise ValueError("an empty bad word")
+            if w not in words:
+                words.append(w)
+        if allowed is not None and not allowed:
+            raise ValueError("Empty allowed_token_ids provided")
+        for name, ids in (("logit_bias", bias), ("allowed_token_ids", allowed or ()), ("bad_words_token_ids", [t for w in words for t in w])):
+            bad = [t for t in ids if not 0 <= t < V]
+            if bad:
+                raise ValueError(f"{name} contains out-of-vocab token ids {bad[:8]} (vocabulary size {V})")
+        if not all(b == b and abs(b) != float("inf") for b in bias.values()):
+            raise ValueError("a logit_bias value is not finite")
+        multi = [w for w in words if len(w) > 1]
+        if len(bias) > ops.MAX_LOGIT_BIAS:
+            raise ValueError(f"{len(bias)} logit_bias entries: at most {ops.MAX_LOGIT_BIAS} are supported")
+        if len(multi) > ops.MAX_BAD_WORDS:
+            raise ValueError(f"{len(multi)} multi-token bad words: at most {ops.MAX_BAD_WORDS} are supported")
+        if any(len(w) > ops.MAX_BAD_WORD_LEN for w in multi):
+            raise ValueError(f"a bad word is longer than {ops.MAX_BAD_WORD_LEN} tokens")
+        single = set(w[0] for w in words if len(w) == 1)
+        left = (set(allowed) if allowed is not None else None)
+        n_left = len(left - single) if left is not None else V - len(single)
+        if n_left <= 0:
+            raise ValueError("every allowed token is a single-token bad word: the request could never emit a token")
+        if stop:
+            gone = single | set(int(t) for t in stop if 0 <= int(t) < V)
+            if (len(left - gone) if left is not None else V - len(gone)) <= 0:
+                raise ValueError("before min_tokens every allowed token is a bad word or a stop id: the request could never "
+                                 "emit a token")
+        want = (tuple(sorted(bias.items())), allowed, tuple(words))
+        if want != self._tc(slot) and self._len_ub[slot] > 0:
+            raise ValueError(f"slot {slot} is occupied: token constraints are set before the request is admitted")
+        return want
+
+    def _constraints_on(self) -> bool:
+        """Some occupied slot carries a token constraint: the cycle is the fourth graph."""
+        return self._tc_host is not None and any(self._tc_host[b] is not None for b in range(self.B) if self._len_ub[b] > 0)
+
+    def _ensure_constraints(self) -> None:
+        if self._tc_host is None:
+            self.tc = ops.TokenConstraints(self.B, self.cfg.vocab_size, self.device)
+            self._tc_host = [None] * self.B
+
     def _sampling_on(self) -> bool:
         return any(self._samp_host[b][0] >= 1e-5 for b in range(self.B) if self._len_ub[b] > 0)
 
     def _processing_on(self) -> bool:
         """Some occupied slot has a non-neutral logit-processor value: the cycle is the third graph."""
-        return self._lp_host is not None and any(self._lp_host[b] != self._LP_NEUTRAL for b in range(self.B)
-                                                 if self._len_ub[b] > 0)
+        return self._constraints_on() or (self._lp_host is not None and any(
+            self._lp_host[b] != self._LP_NEUTRAL for b in range(self.B) if self._len_ub[b] > 0))
 
     def _lp_needs(self, slot: int) -> bool:
         """The slot keeps token counts: one of its penalties is non-neutral (in fp16, as the kernels read it)."""
@@ -475,11 +569,14 @@ class QSpecEngine:
         self._lp_host = [self._LP_NEUTRAL] * B
 
     def _admit_tokens(self, slot: int, tokens: Sequence[int], num_prompt_tokens: Optional[int]) -> None:
-        """Admission: the outputs the request already has (recomputation) and, for a slot with penalties, its table row."""
+        """Admission: the outputs the request already has (recomputation), for a slot with penalties its table row, for a slot
+        with token constraints the tail of those outputs (a bad word may straddle the admission)."""
         if self._lp_host is None:
             return
         npt = len(tokens) if num_prompt_tokens is None else int(num_prompt_tokens)
         base = len(tokens) - npt
+        if self._tc(slot) is not None:
+            ops.token_constraints_set_tail(self.tc, slot, list(tokens)[npt:])
         if self._gen_base_host[slot] != base:
             self.lp_gen_base[slot] = base
             self._gen_base_host[slot] = base
@@ -488,8 +585,15 @@ class QSpecEngine:
             ops.logit_table_set_prompt(self.tok_table, self.counted_len, slot, ids[:npt].contiguous(),
                                        ids[npt:].contiguous() if base else None)
 
-    def _process(self, logits, out, rows_per_seq: int, j_base: int, draft_ids, active_lens, slot_ids=None):
+    def _process(self, logits, out, rows_per_seq: int, j_base: int, draft_ids, active_lens, slot_ids=None,
+                 constrained: Optional[bool] = None):
         T = logits.shape[0]
+        if self._mode_constrained if constrained is None else constrained:
+            return ops.process_logits_constrained(logits, out[:T], self.tok_table, self.lp_rep, self.lp_freq, self.lp_pres,
+                                                  self.lp_min_tokens, self.lp_gen_base, self.gen_lens, self.lp_stop_ids,
+                                                  self.lp_n_stop, *self.tc.arrays(), self.gen_tokens, draft_ids=draft_ids,
+                                                  rows_per_seq=rows_per_seq, j_base=j_base, slot_ids=slot_ids,
+                                                  active_lens=active_lens)
         return ops.process_logits(logits, out[:T], self.tok_table, self.lp_rep, self.lp_freq, self.lp_pres, self.lp_min_tokens,
                                   self.lp_gen_base, self.gen_lens, self.lp_stop_ids, self.lp_n_stop, draft_ids=draft_ids,
                                   rows_per_seq=rows_per_seq, j_base=j_base, slot_ids=slot_ids, active_lens=active_lens)
@@ -687,7 +791,7 @@ class QSpecEngine:
         processing = self._processing_on()
         if processing:   # position j = 0, nothing in flight: catch up with the committed tokens, then the pre-pass
             self._catch_up()
-            logits = self._process(logits, self.proc_logits_d, 1, 0, None, self.eff_lens)
+            logits = self._process(logits, self.proc_logits_d, 1, 0, None, self.eff_lens, constrained=self._constraints_on())
         if self._sampling_on() or processing:   # sampled requests sample (a seeded one: target stream, j = 0); greedy rows take the argmax
             ops.sample_top_k_top_p(logits, self.draft_probs_kbv[0], self.draft_ids_kb[0], self.samp_temp, self.samp_topk,
                                    self.samp_topp, rng_state=self.sampler.rng_state, workspace=self._sample_ws_d,
@@ -714,6 +818,7 @@ class QSpecEngine:
             self._len_ub[b] += self.k + 1
             self._gen_ub[b] += self.k + 1
         # (every rank sees the same requests: the same decisions.)  The processed cycle is the sampling cycle + the pre-pass
+        self._mode_constrained = self._constraints_on()
         self._mode_processing = self._processing_on()
         self._mode_sampling = self._mode_processing or self._sampling_on()
         if not self.use_graph:
@@ -736,11 +841,12 @@ class QSpecEngine:
             self._collect_errors()
 
     def _graph_names(self):
-        return ("_graph_p", "_graph_draft_p") if self._mode_processing else \
+        return ("_graph_c", "_graph_draft_c") if self._mode_constrained else \
+            ("_graph_p", "_graph_draft_p") if self._mode_processing else \
             ("_graph_s", "_graph_draft_s") if self._mode_sampling else ("_graph", "_graph_draft")
 
     def _graphs(self):
-        """(whole-cycle graph, draft-only graph) of the current mode: greedy, sampling or processed."""
+        """(whole-cycle graph, draft-only graph) of the current mode: greedy, sampling, processed or constrained."""
         full, draft = self._graph_names()
         return getattr(self, full), getattr(self, draft)
 

@@ -42,6 +42,7 @@ record and the request, non-driver ranks sit in `start_worker_execution_loop()` 
 """
 from __future__ import annotations
 
+import functools
 import os
 from collections import defaultdict
 from dataclasses import dataclass, field
@@ -78,6 +79,13 @@ class SamplingParams:
     repetition_penalty: float = 1.0
     min_tokens: int = 0
     stop_token_ids: Optional[List[int]] = None   # (a vLLM object also carries all_stop_token_ids: these + the EOS id)
+    # token constraints, applied in front of the processors above (vllm/entrypoints/openai/logits_processors.py:10-86,
+    # vllm/logits_process.py:48-119).  A vLLM object arrives with the first two already lowered into logits_processors and its
+    # bad words as strings; the worker has no tokenizer, so its own field takes token ids.
+    logit_bias: Optional[Dict[Any, float]] = None
+    allowed_token_ids: Optional[List[int]] = None
+    bad_words_token_ids: Optional[List[List[int]]] = None
+    logits_processors: Optional[List[Any]] = None
 
 
 @dataclass
@@ -562,6 +570,7 @@ class SpecDecodeWorker:
                 seed = getattr(sp, "seed", None)   # (forwarded only when set: an engine double need not know the keyword)
                 extra = {} if seed is None else {"seed": seed}
                 lp = self._logit_processor_args(sp)
+                lp.update(self._token_constraint_args(sp))
                 extra.update(lp)
                 self.engine.set_sampling_params(b, getattr(sp, "temperature", 0.0) or 0.0, getattr(sp, "top_k", -1) or -1,
                                                 getattr(sp, "top_p", 1.0) if sp is not None else 1.0, **extra)
@@ -603,6 +612,62 @@ class SpecDecodeWorker:
             if len(stop) > 16:
                 raise ValueError(f"min_tokens with {len(stop)} stop token ids: at most 16 are supported")
             out["stop_token_ids"] = tuple(stop)
+        return out
+
+    @staticmethod
+    def _token_constraint_args(sp) -> Dict[str, Any]:
+        """The logit_bias / allowed_token_ids / bad_words_token_ids keywords of engine.set_sampling_params for a request, EMPTY
+        when it has none.  Sources: the plain fields (logit_bias keys may be strings; the biases are clamped to [-100, 100]
+        as the reference's lowering does, logits_processors.py:62-66) and the three processors that lowering leaves in
+        `logits_processors` (llm_engine.py:1950-2009), recognised by name and attributes -- nothing is imported:
+          functools.partial(logit_bias_logits_processor, {id: bias}); AllowedTokenIdsLogitsProcessor with `allowed_ids`, or,
+          once it has been called (the objects are cached and shared between requests), with `mask` alone (True = forbidden);
+          NoBadWordsLogitsProcessor with `bad_words_ids`.
+        A field and a processor that say the same thing are one constraint: biases are merged by id (the processor's value is
+        the one the reference would apply), allowed sets intersect, bad words are deduplicated.  Any other callable in
+        logits_processors is ignored, as before."""
+        if sp is None:
+            return {}
+        bias: Dict[int, float] = {}
+        allowed = None
+        words: List[Tuple[int, ...]] = []
+        try:
+            for t, b in (getattr(sp, "logit_bias", None) or {}).items():
+                bias[int(t)] = min(100.0, max(-100.0, float(b)))
+        except (TypeError, ValueError) as exc:
+            raise ValueError("Found token_id in logit_bias that is not an integer or string representing an integer") from exc
+        ids = getattr(sp, "allowed_token_ids", None)
+        if ids is not None:
+            allowed = set(int(t) for t in ids)
+            if not allowed:
+                raise ValueError("Empty allowed_token_ids provided")
+        for w in (getattr(sp, "bad_words_token_ids", None) or ()):
+            words.append(tuple(int(t) for t in w))
+        for proc in (getattr(sp, "logits_processors", None) or ()):
+            name = type(proc).__name__
+            if isinstance(proc, functools.partial) and getattr(proc.func, "__name__", "") == "logit_bias_logits_processor" \
+                    and proc.args and isinstance(proc.args[0], dict):
+                for t, b in proc.args[0].items():
+                    bias[int(t)] = float(b)
+            elif name == "AllowedTokenIdsLogitsProcessor" and (getattr(proc, "allowed_ids", None) is not None
+                                                              or getattr(proc, "mask", None) is not None):
+                if getattr(proc, "allowed_ids", None) is not None:
+                    got = set(int(t) for t in proc.allowed_ids)
+                else:
+                    mask = proc.mask.tolist() if hasattr(proc.mask, "tolist") else list(proc.mask)
+                    got = set(i for i, forbidden in enumerate(mask) if not forbidden)
+                allowed = got if allowed is None else allowed & got
+                if not allowed:
+                    raise ValueError("Empty allowed_token_ids provided")
+            elif name == "NoBadWordsLogitsProcessor" and getattr(proc, "bad_words_ids", None) is not None:
+                words.extend(tuple(int(t) for t in w) for w in proc.bad_words_ids)
+        out: Dict[str, Any] = {}
+        if bias:
+            out["logit_bias"] = bias
+        if allowed is not None:
+            out["allowed_token_ids"] = sorted(allowed)
+        if words:
+            out["bad_words_token_ids"] = [list(w) for w in dict.fromkeys(words)]
         return out
 
     def _decode_slots(self, sgml) -> List[int]:

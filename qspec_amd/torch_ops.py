@@ -54,7 +54,14 @@ _op("logit_table_set_prompt(Tensor(a!) tok_table, Tensor(b!) counted_len, int sl
     "Tensor? output_ids=None) -> ()", _none(ops.logit_table_set_prompt))
 _op("logit_table_catch_up(Tensor(a!) tok_table, Tensor(b!) counted_len, Tensor need_counts, Tensor gen_tokens, "
     "Tensor gen_lens) -> ()", _none(ops.logit_table_catch_up))
+# token constraints (logit_bias, allowed_token_ids, bad words) inside the same pre-pass launch
+_op("process_logits_constrained(Tensor logits, Tensor(a!) out, Tensor tok_table, Tensor repetition, Tensor frequency, "
+    "Tensor presence, Tensor min_tokens, Tensor gen_base, Tensor gen_lens, Tensor stop_ids, Tensor num_stop_ids, Tensor deny, "
+    "Tensor meta, Tensor bias_ids, Tensor bias_vals, Tensor words, Tensor word_lens, Tensor tail, Tensor gen_tokens, "
+    "Tensor? draft_ids=None, int rows_per_seq=1, int j_base=0, Tensor? slot_ids=None, Tensor? active_lens=None) -> Tensor(a!)",
+    ops.process_logits_constrained)
 
 OPS = ("rms_norm_general_fuse_sum_i4", "rms_norm_general_fuse_sum_fp16", "fuse_sym_quant", "faster_fast_hadamard_transform",
        "fast_hadamard_transform", "rowwise_scaled_linear_cutlass_s4s4_unified", "w4a16_matmul", "rotary_embedding",
-       "reshape_and_cache_flash", "advance_step_flashattn", "process_logits", "logit_table_set_prompt", "logit_table_catch_up")
+       "reshape_and_cache_flash", "advance_step_flashattn", "process_logits", "logit_table_set_prompt", "logit_table_catch_up",
+       "process_logits_constrained")
