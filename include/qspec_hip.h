@@ -687,6 +687,75 @@ int qspec_qkv_rope_linear_w4a16_xp(const qspec_half* x, const int8_t* wq, const 
 int qspec_gate_up_silu_linear_w4a16_xp(const qspec_half* x, const int8_t* wq, const qspec_half* ws, qspec_half* act, int M,
                                        int intermediate, int K, void* workspace, void* stream);
 
+/* ---------------------------------------------------------------- FP8 KV cache (kv_cache_dtype = "fp8" / "fp8_e4m3")
+ * The `_kv8` entries are the entries of the same name with a BYTE cache: uint8_t key_cache / value_cache in place of the two
+ * qspec_half pointers, followed by float k_scale, v_scale.  Additive: every entry above keeps its signature and its bits.
+ *
+ * Format.  OCP e4m3fn (not fnuz), one byte per element, the fp16 cache's layout [num_blocks, block_size, num_kv_heads,
+ *          head_size].
+ * Write.   byte = e4m3_rne(clamp(float(x) * inv, -448, 448)), inv = 1.0f / scale computed once on the host in fp32; x is
+ *          the fp16 K (post-RoPE) or V value the fp16 form stores.  The clamp is applied in fp32 in front of the convert:
+ *          the byte does not depend on the hardware's overflow mode.  (A NaN stays a NaN.)
+ * Read.    value = float(e4m3) * scale.  Every e4m3 value is an fp16 value, so the attention kernels widen the bytes to
+ *          the fp16 operands of the fp16 form (exact) and keep its arithmetic; k_scale is folded into the softmax scale
+ *          (sm_scale * k_scale, an fp32 product on the host), v_scale multiplies a row's output or partial `o` where it is
+ *          stored.  The (o, m, l) partials left for qspec_heads_hadamard_merged* carry it: those consumers are unchanged.
+ * Scales.  Per layer, per tensor, fp32, positive and finite, default 1.0 (vllm/model_executor/layers/quantization/
+ *          kv_cache.py); a checkpoint stores them as model.layers.{i}.self_attn.k_scale / .v_scale. */
+/* torch.ops._C_cache_ops.reshape_and_cache_flash(key, value, key_cache, value_cache, slot_mapping, "fp8", k_scale, v_scale)
+ *   csrc/cache_kernels.cu:207-303: the write half of the contract above. */
+int qspec_reshape_and_cache_flash_kv8(const qspec_half* key, const qspec_half* value, uint8_t* key_cache,
+                                      uint8_t* value_cache, float k_scale, float v_scale, const int64_t* slot_mapping,
+                                      int tokens, int num_kv_heads, int head_size, int64_t key_stride,
+                                      int64_t value_stride, void* stream);
+
+/* qspec_rope_kv_write with the cache write of reshape_and_cache_flash(..., "fp8", k_scale, v_scale); the qkv row is rotated in
+ * place exactly as by the fp16 form. */
+int qspec_rope_kv_write_kv8(const int64_t* positions, qspec_half* qkv, const qspec_half* cos_sin_cache,
+                            uint8_t* key_cache, uint8_t* value_cache, float k_scale, float v_scale,
+                            const int64_t* slot_mapping, int tokens, int num_heads, int num_kv_heads, int head_size,
+                            int rot_dim, void* stream);
+
+/* qspec_paged_attention over an fp8 cache (vllm/attention/ops/paged_attn.py: kv_cache_dtype = "fp8", k_scale, v_scale): the read
+ * half of the contract above.  Same dispatch rule, workspace and partials as the fp16 form; the scalar kernel of odd head
+ * sizes has no fp8 form (head_size % 8 == 0 is required). */
+int qspec_paged_attention_kv8(const qspec_half* q, int64_t q_stride, const uint8_t* key_cache,
+                              const uint8_t* value_cache, float k_scale, float v_scale, const int32_t* block_tables,
+                              int max_blocks_per_seq, const int32_t* ctx_lens, const int32_t* q_start, int n_seqs,
+                              int tokens, int max_q_len, int num_heads, int num_kv_heads, int head_size,
+                              int block_size, float sm_scale, int n_splits, void* workspace, qspec_half* out,
+                              void* stream);
+
+/* The fused qkv + RoPE + cache-write GEMMs with the cache write of reshape_and_cache_flash(..., "fp8", k_scale, v_scale): the
+ * same launches (no separate quantising launch), the fp16 qkv row bit-identical to the fp16-cache form. */
+int qspec_qkv_rope_linear_s4s4_kv8(const int8_t* xq, const qspec_half* xs, const int8_t* wq, const qspec_half* ws,
+                                   qspec_half* qkv, int M, int N, int K, const int64_t* positions,
+                                   const qspec_half* cos_sin_cache, uint8_t* key_cache, uint8_t* value_cache,
+                                   float k_scale, float v_scale, const int64_t* slot_mapping, int num_heads,
+                                   int num_kv_heads, int head_size, int rot_dim, void* stream);
+int qspec_qkv_rope_linear_w4a16_kv8(const qspec_half* x, const int8_t* wq, const qspec_half* ws, qspec_half* qkv,
+                                    int M, int N, int K, const int64_t* positions, const qspec_half* cos_sin_cache,
+                                    uint8_t* key_cache, uint8_t* value_cache, float k_scale, float v_scale,
+                                    const int64_t* slot_mapping, int num_heads, int num_kv_heads, int head_size,
+                                    int rot_dim, void* workspace, void* stream);
+int qspec_qkv_rope_linear_w4a16_xp_kv8(const qspec_half* x, const int8_t* wq, const qspec_half* ws, qspec_half* qkv,
+                                       int M, int N, int K, const int64_t* positions, const qspec_half* cos_sin_cache,
+                                       uint8_t* key_cache, uint8_t* value_cache, float k_scale, float v_scale,
+                                       const int64_t* slot_mapping, int num_heads, int num_kv_heads, int head_size,
+                                       int rot_dim, void* workspace, void* stream);
+int qspec_qkv_rope_linear_w4a16_xp32_kv8(const qspec_half* x, const int8_t* wq, const qspec_half* ws, qspec_half* qkv,
+                                         int M, int N, int K, const int64_t* positions,
+                                         const qspec_half* cos_sin_cache, uint8_t* key_cache, uint8_t* value_cache,
+                                         float k_scale, float v_scale, const int64_t* slot_mapping, int num_heads,
+                                         int num_kv_heads, int head_size, int rot_dim, void* stream);
+int qspec_ln_qkv_rope_linear_s4s4_kv8(const qspec_half* hidden_in, const qspec_half* delta, qspec_half* hidden_out,
+                                      float eps, const int8_t* wq, const qspec_half* ws, qspec_half* qkv, int M,
+                                      int N, int K, const int64_t* positions, const qspec_half* cos_sin_cache,
+                                      uint8_t* key_cache, uint8_t* value_cache, float k_scale, float v_scale,
+                                      const int64_t* slot_mapping, int num_heads, int num_kv_heads, int head_size,
+                                      int rot_dim, void* sync_workspace, void* stream);
+
+
 #ifdef __cplusplus
 }
 #endif

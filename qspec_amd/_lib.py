@@ -82,6 +82,20 @@ SIGNATURES = {
     "qspec_paged_attention_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "qspec_paged_attention": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp,
                                    _vp, _vp]),
+    "qspec_reshape_and_cache_flash_kv8": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _i, _i, _i64, _i64, _vp]),
+    "qspec_rope_kv_write_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _i, _i, _i, _i, _i, _vp]),
+    "qspec_paged_attention_kv8": (_i, [_vp, _i64, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i,
+                                       _f, _i, _vp, _vp, _vp]),
+    "qspec_qkv_rope_linear_s4s4_kv8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp,
+                                            _i, _i, _i, _i, _vp]),
+    "qspec_qkv_rope_linear_w4a16_kv8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _i,
+                                             _i, _i, _i, _vp, _vp]),
+    "qspec_qkv_rope_linear_w4a16_xp_kv8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _i,
+                                                _i, _i, _i, _vp, _vp]),
+    "qspec_qkv_rope_linear_w4a16_xp32_kv8": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp,
+                                                  _i, _i, _i, _i, _vp]),
+    "qspec_ln_qkv_rope_linear_s4s4_kv8": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _f,
+                                               _f, _vp, _i, _i, _i, _i, _vp, _vp]),
     "qspec_embedding": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "qspec_sampler_workspace_bytes": (_sz, [_i]),
     "qspec_softmax_argmax": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),

@@ -10,6 +10,8 @@ The reference reads two safetensors shards, renames three key fragments and fuse
     mlp.{up,gate}_proj.weight / .weight_scales
     mlp.down_proj.0.had_rem_dim            fp16/fp32 [28, 28]  (`down_proj.0.` -> `online_hadamard.`)
     mlp.down_proj.2.weight / .weight_scales                    (`down_proj.2.` -> `down_proj.`)
+    self_attn.k_scale / self_attn.v_scale  fp32 scalars, OPTIONAL: per-tensor scales of an fp8 KV cache
+                                           (vllm/model_executor/layers/quantization/kv_cache.py); absent or <= 0 -> 1.0
   plus `model.embed_tokens.weight` and `lm_head.weight` (fp16); no norm weights (folded in offline,
   third-party/QuaRot/e2e/checkpoint_utils/quantize_llama_checkpoint.py:92-99).
 
@@ -84,6 +86,14 @@ def load_state_dict(model, sd: Dict[str, torch.Tensor], strict: bool = True):
         if row != lin.weight.shape[0]:
             raise ValueError(f"{prefix}: {parts} give {row} rows, the fused projection has {lin.weight.shape[0]}")
 
+    def kv_scale(key):
+        """kv_cache.py: a missing scale, or one that is not positive, is 1.0."""
+        if key not in sd:
+            return 1.0
+        v = float(take(key).reshape(-1)[0])
+        return v if v > 0.0 and v < float("inf") else 1.0
+
+    scales = []
     model.embed_tokens.copy_(take("model.embed_tokens.weight", model.embed_tokens.shape).to(torch.float16))
     model.lm_head.copy_(take("lm_head.weight", model.lm_head.shape).to(torch.float16))
     for i, layer in enumerate(model.layers):
@@ -92,6 +102,7 @@ def load_state_dict(model, sd: Dict[str, torch.Tensor], strict: bool = True):
         put_linear(layer.o_proj, ("o_proj",), f"{p}.self_attn")
         put_linear(layer.gate_up, ("up_proj", "gate_proj"), f"{p}.mlp")                     # :301-314, up FIRST
         put_linear(layer.down_proj, ("down_proj",), f"{p}.mlp")
+        scales.append(tuple(kv_scale(f"{p}.self_attn.{n}") for n in ("k_scale", "v_scale")))
         hk = f"{p}.mlp.online_hadamard.had_rem_dim"
         if hk in sd:
             had = take(hk)
@@ -104,6 +115,7 @@ def load_state_dict(model, sd: Dict[str, torch.Tensor], strict: bool = True):
                 model.had_rem_dim.copy_(h16)
             elif not torch.equal(h16, model.had_rem_dim):
                 raise ValueError(f"`{hk}` differs from layer 0's table")
+    model.kv_scales = None if all(s == (1.0, 1.0) for s in scales) else scales
     if strict:
         extra = sorted(k for k in sd if k not in used and not k.endswith("rotary_emb.inv_freq"))
         if extra:
@@ -133,6 +145,8 @@ def reference_state_dict(model) -> Dict[str, torch.Tensor]:
             out[f"{prefix}.{disk_name(name)}.weight_scales"] = lin.weight_scales.view(-1)[row:row + n].detach().cpu().view(-1, 1).contiguous()
             row += n
 
+    kvs = getattr(model, "kv_scales", None)
+    write_scales = kvs is not None and any((float(a), float(b)) != (1.0, 1.0) for a, b in kvs)
     for i, layer in enumerate(model.layers):
         p = f"model.layers.{i}"
         split(layer.qkv_proj, (("q_proj", q), ("k_proj", kv), ("v_proj", kv)), f"{p}.self_attn")
@@ -141,6 +155,10 @@ def reference_state_dict(model) -> Dict[str, torch.Tensor]:
         split(layer.down_proj, (("down_proj.2", cfg.hidden_size),), f"{p}.mlp")
         if model.had_rem_dim is not None:
             out[f"{p}.mlp.down_proj.0.had_rem_dim"] = model.had_rem_dim.detach().cpu().contiguous()
+        if write_scales:   # written only when they are not all 1.0
+            ks, vs = model.kv_scales[i]
+            out[f"{p}.self_attn.k_scale"] = torch.tensor(float(ks), dtype=torch.float32)
+            out[f"{p}.self_attn.v_scale"] = torch.tensor(float(vs), dtype=torch.float32)
     return out
 
 

@@ -49,38 +49,66 @@ int rotary_embedding(const int64_t* positions, f16* q, f16* k, const f16* cos_si
     return 0;
 }
 
+// KVT = f16: the cache element is the fp16 value.  KVT = uint8_t: the e4m3 byte of f(value) * inv (common.cuh: f2e4m3),
+// at the same element position -- reshape_and_cache_flash(..., "fp8", k_scale, v_scale), inv = 1 / scale.
+template <typename KVT>
+__device__ __forceinline__ KVT kv_elem(f16 v, float inv) {
+    if constexpr (sizeof(KVT) == 1) return f2e4m3(h2f(v) * inv);
+    else return v;
+}
+// eight consecutive elements: one 16-byte (fp16) or one 8-byte (e4m3) store
+template <typename KVT>
+__device__ __forceinline__ void kv_store8(KVT* dst, f16x8 v, float inv) {
+    if constexpr (sizeof(KVT) == 1) {
+        u32x2 w;
+        w[0] = f2e4m3_x4(h2f(v[0]) * inv, h2f(v[1]) * inv, h2f(v[2]) * inv, h2f(v[3]) * inv);
+        w[1] = f2e4m3_x4(h2f(v[4]) * inv, h2f(v[5]) * inv, h2f(v[6]) * inv, h2f(v[7]) * inv);
+        *reinterpret_cast<u32x2*>(dst) = w;
+    } else {
+        *reinterpret_cast<f16x8*>(dst) = v;
+    }
+}
+
+template <typename KVT>
 __global__ __launch_bounds__(256) void reshape_and_cache_flash_kernel(const f16* __restrict__ key,
                                                                       const f16* __restrict__ value,
-                                                                      f16* __restrict__ key_cache,
-                                                                      f16* __restrict__ value_cache,
+                                                                      KVT* __restrict__ key_cache,
+                                                                      KVT* __restrict__ value_cache,
                                                                       const int64_t* __restrict__ slot_mapping, int n,
-                                                                      int64_t k_stride, int64_t v_stride) {
+                                                                      int64_t k_stride, int64_t v_stride, float k_inv,
+                                                                      float v_inv) {
     const int t = blockIdx.x;
     const int64_t slot = slot_mapping[t];
     if (slot < 0) return;  // padded token
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        key_cache[slot * n + i] = key[t * k_stride + i];
-        value_cache[slot * n + i] = value[t * v_stride + i];
+        key_cache[slot * n + i] = kv_elem<KVT>(key[t * k_stride + i], k_inv);
+        value_cache[slot * n + i] = kv_elem<KVT>(value[t * v_stride + i], v_inv);
     }
 }
 
-int reshape_and_cache_flash(const f16* key, const f16* value, f16* key_cache, f16* value_cache,
+int reshape_and_cache_flash(const f16* key, const f16* value, void* key_cache, void* value_cache,
                             const int64_t* slot_mapping, int T, int nkv, int d, int64_t k_stride, int64_t v_stride,
-                            hipStream_t st) {
+                            hipStream_t st, KvQuant kq) {
     if (T == 0) return 0;
-    hipLaunchKernelGGL(reshape_and_cache_flash_kernel, dim3(T), dim3(256), 0, st, key, value, key_cache, value_cache,
-                       slot_mapping, nkv * d, k_stride, v_stride);
+    if (kq.fp8)
+        hipLaunchKernelGGL(reshape_and_cache_flash_kernel<uint8_t>, dim3(T), dim3(256), 0, st, key, value,
+                           (uint8_t*)key_cache, (uint8_t*)value_cache, slot_mapping, nkv * d, k_stride, v_stride, kq.k_inv,
+                           kq.v_inv);
+    else
+        hipLaunchKernelGGL(reshape_and_cache_flash_kernel<f16>, dim3(T), dim3(256), 0, st, key, value, (f16*)key_cache,
+                           (f16*)value_cache, slot_mapping, nkv * d, k_stride, v_stride, 1.0f, 1.0f);
     return 0;
 }
 
 // Fused: in-place RoPE on the q and k slices of the fused qkv row, then scatter k,v into the paged cache.
 // qkv [T, (nq + 2 nkv) * d]; one workgroup per token, 8 fp16 (16 B) per lane trip.
+template <typename KVT>
 __global__ __launch_bounds__(256) void rope_kv_write_kernel(const int64_t* __restrict__ positions,
                                                             f16* __restrict__ qkv,
                                                             const f16* __restrict__ cos_sin_cache,
-                                                            f16* __restrict__ key_cache, f16* __restrict__ value_cache,
+                                                            KVT* __restrict__ key_cache, KVT* __restrict__ value_cache,
                                                             const int64_t* __restrict__ slot_mapping, int nq, int nkv,
-                                                            int d, int rot_dim) {
+                                                            int d, int rot_dim, float k_inv, float v_inv) {
     const int t = blockIdx.x;
     const int embed = rot_dim / 2;
     const int row = (nq + 2 * nkv) * d;
@@ -103,31 +131,35 @@ __global__ __launch_bounds__(256) void rope_kv_write_kernel(const int64_t* __res
         *reinterpret_cast<f16x8*>(hp + o) = x;
         *reinterpret_cast<f16x8*>(hp + embed + o) = y;
         if (h >= nq && slot >= 0) {
-            f16* kc = key_cache + (slot * nkv + (h - nq)) * d;
-            *reinterpret_cast<f16x8*>(kc + o) = x;
-            *reinterpret_cast<f16x8*>(kc + embed + o) = y;
+            KVT* kc = key_cache + (slot * nkv + (h - nq)) * d;
+            kv_store8<KVT>(kc + o, x, k_inv);
+            kv_store8<KVT>(kc + embed + o, y, k_inv);
         }
     }
     if (slot >= 0) {
         const f16* vsrc = base + (size_t)(nq + nkv) * d;
-        f16* vc = value_cache + slot * nkv * d;
+        KVT* vc = value_cache + slot * nkv * d;
         for (int i = threadIdx.x; i < nkv * d / 8; i += blockDim.x)
-            *reinterpret_cast<f16x8*>(vc + 8 * i) = *reinterpret_cast<const f16x8*>(vsrc + 8 * i);
+            kv_store8<KVT>(vc + 8 * i, *reinterpret_cast<const f16x8*>(vsrc + 8 * i), v_inv);
         if (rot_dim < d) {  // un-rotated tail of k
             for (int i = threadIdx.x; i < nkv * (d - rot_dim); i += blockDim.x) {
                 int h = i / (d - rot_dim), o = rot_dim + i % (d - rot_dim);
-                key_cache[(slot * nkv + h) * d + o] = base[(size_t)(nq + h) * d + o];
+                key_cache[(slot * nkv + h) * d + o] = kv_elem<KVT>(base[(size_t)(nq + h) * d + o], k_inv);
             }
         }
     }
 }
 
-int rope_kv_write(const int64_t* positions, f16* qkv, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                  const int64_t* slot_mapping, int T, int nq, int nkv, int d, int rot_dim, hipStream_t st) {
+int rope_kv_write(const int64_t* positions, f16* qkv, const f16* cos_sin_cache, void* key_cache, void* value_cache,
+                  const int64_t* slot_mapping, int T, int nq, int nkv, int d, int rot_dim, hipStream_t st, KvQuant kq) {
     if (T == 0) return 0;
     if (rot_dim > d || rot_dim % 16 || d % 8) return -1;
-    hipLaunchKernelGGL(rope_kv_write_kernel, dim3(T), dim3(256), 0, st, positions, qkv, cos_sin_cache, key_cache,
-                       value_cache, slot_mapping, nq, nkv, d, rot_dim);
+    if (kq.fp8)
+        hipLaunchKernelGGL(rope_kv_write_kernel<uint8_t>, dim3(T), dim3(256), 0, st, positions, qkv, cos_sin_cache,
+                           (uint8_t*)key_cache, (uint8_t*)value_cache, slot_mapping, nq, nkv, d, rot_dim, kq.k_inv, kq.v_inv);
+    else
+        hipLaunchKernelGGL(rope_kv_write_kernel<f16>, dim3(T), dim3(256), 0, st, positions, qkv, cos_sin_cache,
+                           (f16*)key_cache, (f16*)value_cache, slot_mapping, nq, nkv, d, rot_dim, 1.0f, 1.0f);
     return 0;
 }
 
@@ -197,12 +229,16 @@ __device__ __forceinline__ void lds_read_tr_b16_x16(uint32_t a, u32x2 (&lo)[8], 
 // so v_readlane + SALU instead of 20 ds_bpermute -- is what paged_attention_waves_kernel<.., FAST> uses; HERE it measured
 // slower, 6.16 against 6.05 us per launch and 7.57 against 7.53 ms per cycle: the serial SALU chain is longer than the
 // pipelined permutes.)
-template <bool PF, bool BT>
+// KVT = uint8_t (fp8 KV cache): a K / V piece of eight elements is an 8-byte load of e4m3 bytes, held as loaded and widened to
+// the eight halves of the fp16 form at its first use (exact); LDS, MFMAs and softmax see the same fp16 operands either way.
+// sm_scale arrives with k_scale folded in; v_scale multiplies the split's output where the partial is stored.
+template <bool PF, bool BT, typename KVT>
 __global__ __launch_bounds__(256) void paged_attention_kernel(
-    const f16* __restrict__ q, int64_t q_stride, const f16* __restrict__ key_cache, const f16* __restrict__ value_cache,
+    const f16* __restrict__ q, int64_t q_stride, const KVT* __restrict__ key_cache, const KVT* __restrict__ value_cache,
     const int32_t* __restrict__ block_tables, int max_blocks, const int32_t* __restrict__ ctx_lens,
     const int32_t* __restrict__ q_start, int nq, int nkv, int bs_log2, int group_log2, float sm_scale, int n_splits,
-    int n_rb, int* cnt, float* ws_o, float* ws_ml, f16* __restrict__ out, int merge) {
+    int n_rb, int* cnt, float* ws_o, float* ws_ml, f16* __restrict__ out, int merge, float v_scale) {
+    constexpr bool FP8 = sizeof(KVT) == 1;
     constexpr int D = 128;
 #ifdef QS_ATT_STAMPS
     long long stamp[10];
@@ -266,7 +302,7 @@ __global__ __launch_bounds__(256) void paged_attention_kernel(
         int64_t k[2], v[8];
     };
     struct KV {
-        u32x4 kfrag[2][4], vraw[8];
+        typename KvRaw<KVT>::type kfrag[2][4], vraw[8];
     };
     // Keys past the split's end are masked after the load; their ADDRESSES are those of the split's last key, so that a
     // 64-key split does not pull the neighbouring split's 64 keys through this CU as well (a chunk is 128 keys: twice the
@@ -289,13 +325,13 @@ __global__ __launch_bounds__(256) void paged_attention_kernel(
     auto fetch = [&](KV& kv, const Slots& sl) {
 #pragma unroll
         for (int t2 = 0; t2 < 2; t2++) {  // lane (key c16 of tile 2w+t2, d slice 8*g4 + 32j)
-            const f16* kp = key_cache + sl.k[t2] + g4 * 8;
+            const KVT* kp = key_cache + sl.k[t2] + g4 * 8;
 #pragma unroll
-            for (int j = 0; j < 4; j++) kv.kfrag[t2][j] = *reinterpret_cast<const u32x4*>(kp + 32 * j);
+            for (int j = 0; j < 4; j++) kv.kfrag[t2][j] = kv_load8<KVT>(kp + 32 * j);
         }
 #pragma unroll
-        for (int i = 0; i < 8; i++)  // 16 lanes cover one 256-byte V row; wave w, group g4 -> keys 4w+g4 + 16i
-            kv.vraw[i] = *reinterpret_cast<const u32x4*>(value_cache + sl.v[i] + c16 * 8);
+        for (int i = 0; i < 8; i++)  // 16 lanes cover one V row (256 bytes of fp16); wave w, group g4 -> keys 4w+g4 + 16i
+            kv.vraw[i] = kv_load8<KVT>(value_cache + sl.v[i] + c16 * 8);
     };
     Slots sl_cur, sl_nxt;
     lookup(sl_cur, k_begin);
@@ -330,7 +366,7 @@ __global__ __launch_bounds__(256) void paged_attention_kernel(
 #pragma unroll
             for (int j = 0; j < 4; j++)
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, qfrag[j]),
-                                                             __builtin_bit_cast(f16x8, kv.kfrag[t2][j]), acc, 0, 0, 0);
+                                                             __builtin_bit_cast(f16x8, kv_f16x8(kv.kfrag[t2][j])), acc, 0, 0, 0);
             const int kk = (wave * 2 + t2) * 16 + c16;  // lane holds rows 4*g4 + reg of key column kk
             const int p = kb + kk;
 #pragma unroll
@@ -345,12 +381,12 @@ __global__ __launch_bounds__(256) void paged_attention_kernel(
 #pragma unroll
             for (int i = 0; i < 8; i++)
                 if (16 * i < nkeys)
-                    *reinterpret_cast<u32x4*>(vl + (wave * 4 + g4 + 16 * i) * QS_ATT_VSTRIDE + c16 * 8) = kv.vraw[i];
+                    *reinterpret_cast<u32x4*>(vl + (wave * 4 + g4 + 16 * i) * QS_ATT_VSTRIDE + c16 * 8) = kv_f16x8(kv.vraw[i]);
         } else {
 #pragma unroll
             for (int i = 0; i < 8; i++) {
                 const int kk = wave * 4 + g4 + 16 * i;
-                const u32x4 vz = kk < nkeys ? kv.vraw[i] : u32x4{0, 0, 0, 0};
+                const u32x4 vz = kk < nkeys ? kv_f16x8(kv.vraw[i]) : u32x4{0, 0, 0, 0};
                 if (16 * i < ((nkeys + 31) & ~31)) *reinterpret_cast<u32x4*>(vl + kk * QS_ATT_VSTRIDE + c16 * 8) = vz;
             }
         }
@@ -464,8 +500,13 @@ __global__ __launch_bounds__(256) void paged_attention_kernel(
             const int rr = r0 + r;
             const int tok = qs + (rr >> group_log2), head = (kvh << group_log2) + (rr & gmask);
             float* dst = ws_o + (((size_t)tok * nq + head) * n_splits + split) * D + wave * 32 + c16;
-            dst[0] = o0[reg];
-            dst[16] = o1[reg];
+            if constexpr (FP8) {
+                dst[0] = o0[reg] * v_scale;
+                dst[16] = o1[reg] * v_scale;
+            } else {
+                dst[0] = o0[reg];
+                dst[16] = o1[reg];
+            }
         }
     }
     if (tid < R) {
@@ -592,12 +633,13 @@ __global__ __launch_bounds__(256) void paged_attention_kernel(
 // registers -- and every K / V address is a uniform 64-bit base (SALU) plus a lane offset that never changes.  The
 // general form spends ~250 of its ~700 loop instructions on lane permutes and 64-bit address arithmetic per slice and
 // needs AGPR copies (291 VGPRs); at one wave per SIMD the instruction count IS the slice time.
-template <bool BT, int NW, bool FAST>   // BT: block-table row in registers, lookups as lane permutes (see paged_attention_kernel)
+template <bool BT, int NW, bool FAST, typename KVT>   // BT: block-table row in registers, lookups as lane permutes; KVT: see paged_attention_kernel
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void paged_attention_waves_kernel(
-    const f16* __restrict__ q, int64_t q_stride, const f16* __restrict__ key_cache, const f16* __restrict__ value_cache,
+    const f16* __restrict__ q, int64_t q_stride, const KVT* __restrict__ key_cache, const KVT* __restrict__ value_cache,
     const int32_t* __restrict__ block_tables, int max_blocks, const int32_t* __restrict__ ctx_lens,
     const int32_t* __restrict__ q_start, int nq, int nkv, int bs_log2, int group_log2, float sm_scale, int n_splits,
-    int n_rb, float* __restrict__ ws_o, float* __restrict__ ws_ml) {
+    int n_rb, float* __restrict__ ws_o, float* __restrict__ ws_ml, float v_scale) {
+    constexpr bool FP8 = sizeof(KVT) == 1;
     constexpr int D = 128, PSTR = 40;   // P row stride in halves (80 B)
     constexpr int WAVE_LDS = QS_AW_KEYS * QS_ATT_VSTRIDE * 2 + 2 * 16 * PSTR * 2;   // V tile + P hi/lo tile, bytes
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -638,7 +680,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void paged_attention_wave
         int64_t k[2], v[8];
     };
     struct KV {
-        u32x4 kf[2][4], vr[8];
+        typename KvRaw<KVT>::type kf[2][4], vr[8];
     };
     auto lookup = [&](Slots& sl, int sb) {   // clamped: no load behind a branch
 #pragma unroll
@@ -672,26 +714,26 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void paged_attention_wave
     auto fetch_k_u = [&](KV& kv, const int64_t (&base)[2]) {
 #pragma unroll
         for (int t2 = 0; t2 < 2; t2++) {
-            const f16* kp = key_cache + base[t2] + k_lane;
+            const KVT* kp = key_cache + base[t2] + k_lane;
 #pragma unroll
-            for (int j = 0; j < 4; j++) kv.kf[t2][j] = *reinterpret_cast<const u32x4*>(kp + 32 * j);
+            for (int j = 0; j < 4; j++) kv.kf[t2][j] = kv_load8<KVT>(kp + 32 * j);
         }
     };
     auto fetch_v_u = [&](KV& kv, const int64_t (&base)[2]) {
 #pragma unroll
         for (int i = 0; i < 8; i++)
-            kv.vr[i] = *reinterpret_cast<const u32x4*>(value_cache + base[i >> 2] + (int64_t)((i & 3) * v_step) + v_lane);
+            kv.vr[i] = kv_load8<KVT>(value_cache + base[i >> 2] + (int64_t)((i & 3) * v_step) + v_lane);
     };
     auto fetch = [&](KV& kv, const Slots& sl) {
 #pragma unroll
         for (int t2 = 0; t2 < 2; t2++) {   // lane (key c16 of tile t2, d slice 8 g4 + 32 j)
-            const f16* kp = key_cache + (sl.k[t2] * nkv + kvh) * D + g4 * 8;
+            const KVT* kp = key_cache + (sl.k[t2] * nkv + kvh) * D + g4 * 8;
 #pragma unroll
-            for (int j = 0; j < 4; j++) kv.kf[t2][j] = *reinterpret_cast<const u32x4*>(kp + 32 * j);
+            for (int j = 0; j < 4; j++) kv.kf[t2][j] = kv_load8<KVT>(kp + 32 * j);
         }
 #pragma unroll
-        for (int i = 0; i < 8; i++)   // 16 lanes cover one 256-byte V row: key 4 i + g4 of the slice
-            kv.vr[i] = *reinterpret_cast<const u32x4*>(value_cache + (sl.v[i] * nkv + kvh) * D + c16 * 8);
+        for (int i = 0; i < 8; i++)   // 16 lanes cover one V row: key 4 i + g4 of the slice
+            kv.vr[i] = kv_load8<KVT>(value_cache + (sl.v[i] * nkv + kvh) * D + c16 * 8);
     };
 #ifdef QS_ATT_STAMPS
     long long awst[24];
@@ -754,7 +796,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void paged_attention_wave
 #pragma unroll
             for (int j = 0; j < 4; j++)
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, qfrag[j]),
-                                                             __builtin_bit_cast(f16x8, cur.kf[t2][j]), acc, 0, 0, 0);
+                                                             __builtin_bit_cast(f16x8, kv_f16x8(cur.kf[t2][j])), acc, 0, 0, 0);
             const int kk = t2 * 16 + c16, p = sb + kk;
 #pragma unroll
             for (int reg = 0; reg < 4; reg++)
@@ -767,9 +809,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void paged_attention_wave
         } else {
 #pragma unroll
             for (int t2 = 0; t2 < 2; t2++) {
-                const f16* kp = key_cache + (sl_nxt.k[t2] * nkv + kvh) * D + g4 * 8;
+                const KVT* kp = key_cache + (sl_nxt.k[t2] * nkv + kvh) * D + g4 * 8;
 #pragma unroll
-                for (int j = 0; j < 4; j++) cur.kf[t2][j] = *reinterpret_cast<const u32x4*>(kp + 32 * j);
+                for (int j = 0; j < 4; j++) cur.kf[t2][j] = kv_load8<KVT>(kp + 32 * j);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -777,12 +819,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void paged_attention_wave
         if (nkeys == QS_AW_KEYS) {   // uniform; LDS stores only (no global load sits behind this branch)
 #pragma unroll
             for (int i = 0; i < 8; i++)
-                *reinterpret_cast<u32x4*>(vl + (i * 4 + g4) * QS_ATT_VSTRIDE + c16 * 8) = cur.vr[i];
+                *reinterpret_cast<u32x4*>(vl + (i * 4 + g4) * QS_ATT_VSTRIDE + c16 * 8) = kv_f16x8(cur.vr[i]);
         } else {
 #pragma unroll
             for (int i = 0; i < 8; i++) {
                 const int kk = i * 4 + g4;
-                const u32x4 vz = kk < nkeys ? cur.vr[i] : u32x4{0, 0, 0, 0};
+                const u32x4 vz = kk < nkeys ? kv_f16x8(cur.vr[i]) : u32x4{0, 0, 0, 0};
                 *reinterpret_cast<u32x4*>(vl + kk * QS_ATT_VSTRIDE + c16 * 8) = vz;
             }
         }
@@ -792,7 +834,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void paged_attention_wave
         } else {
 #pragma unroll
             for (int i = 0; i < 8; i++)
-                cur.vr[i] = *reinterpret_cast<const u32x4*>(value_cache + (sl_nxt.v[i] * nkv + kvh) * D + c16 * 8);
+                cur.vr[i] = kv_load8<KVT>(value_cache + (sl_nxt.v[i] * nkv + kvh) * D + c16 * 8);
         }
         __builtin_amdgcn_sched_barrier(0);
         QS_AWST_NW();   // QK + refills issued + V in LDS
@@ -886,6 +928,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void paged_attention_wave
             const int rr = r0 + r;
             const size_t th = (size_t)(qs + (rr >> group_log2)) * nq + (kvh << group_log2) + (rr & gmask);
             float* dst = ws_o + (th * n_splits + split) * D + c8;
+            if constexpr (FP8) {
+#pragma unroll
+                for (int e = 0; e < 8; e++) acc8[e] *= v_scale;
+            }
             *reinterpret_cast<float4*>(dst) = float4{acc8[0], acc8[1], acc8[2], acc8[3]};
             *reinterpret_cast<float4*>(dst + 4) = float4{acc8[4], acc8[5], acc8[6], acc8[7]};
             if ((tid & 15) == 0) {
@@ -917,12 +963,14 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void paged_attention_wave
 //     normalised into `out`.
 #define QS_FA_ROWS 64
 #define QS_FA_KEYS 64
+template <typename KVT>   // see paged_attention_kernel
 __global__ __launch_bounds__(256) void paged_attention_prefill_kernel(
-    const f16* __restrict__ q, int64_t q_stride, const f16* __restrict__ key_cache, const f16* __restrict__ value_cache,
+    const f16* __restrict__ q, int64_t q_stride, const KVT* __restrict__ key_cache, const KVT* __restrict__ value_cache,
     const int32_t* __restrict__ block_tables, int max_blocks, const int32_t* __restrict__ ctx_lens,
     const int32_t* __restrict__ q_start, int nq, int nkv, int bs_log2, int group_log2, float sm_scale, int n_rb,
-    float* __restrict__ ws_o, float* __restrict__ ws_ml, f16* __restrict__ out) {
+    float* __restrict__ ws_o, float* __restrict__ ws_ml, f16* __restrict__ out, float v_scale) {
     constexpr int D = 128;
+    constexpr bool FP8 = sizeof(KVT) == 1;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     unsigned char* kl = reinterpret_cast<unsigned char*>(smem_raw);                       // [64 keys][256 B], swizzled
     f16* vl = reinterpret_cast<f16*>(kl + QS_FA_KEYS * 256);                               // [64 keys][QS_ATT_VSTRIDE]
@@ -975,16 +1023,16 @@ __global__ __launch_bounds__(256) void paged_attention_prefill_kernel(
 
     // staging: thread (key = tid / 4, quarter = tid % 4) moves 64 B of the key's K row and of its V row
     const int skey = tid >> 2, spart = tid & 3;
-    u32x4 kreg[4], vreg[4];
+    typename KvRaw<KVT>::type kreg[4], vreg[4];
     auto stage_load = [&](int kb) {   // unconditional, clamped (no load behind a branch)
         const int p = min(kb + skey, ctx - 1);
         const int64_t slot = ((int64_t)bt[min(p >> bs_log2, max_blocks - 1)] << bs_log2) + (p & bmask);
-        const f16* kp = key_cache + (slot * nkv + kvh) * D + spart * 32;
-        const f16* vp = value_cache + (slot * nkv + kvh) * D + spart * 32;
+        const KVT* kp = key_cache + (slot * nkv + kvh) * D + spart * 32;
+        const KVT* vp = value_cache + (slot * nkv + kvh) * D + spart * 32;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            kreg[i] = *reinterpret_cast<const u32x4*>(kp + 8 * i);
-            vreg[i] = *reinterpret_cast<const u32x4*>(vp + 8 * i);
+            kreg[i] = kv_load8<KVT>(kp + 8 * i);
+            vreg[i] = kv_load8<KVT>(vp + 8 * i);
         }
     };
     stage_load(0);
@@ -994,8 +1042,8 @@ __global__ __launch_bounds__(256) void paged_attention_prefill_kernel(
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int ci = spart * 4 + i;
-            *reinterpret_cast<u32x4*>(kl + skey * 256 + ((ci ^ (skey & 15)) << 4)) = kreg[i];
-            const u32x4 vz = skey < nk ? vreg[i] : u32x4{0, 0, 0, 0};   // zero rows keep the MFMA clean
+            *reinterpret_cast<u32x4*>(kl + skey * 256 + ((ci ^ (skey & 15)) << 4)) = kv_f16x8(kreg[i]);
+            const u32x4 vz = skey < nk ? kv_f16x8(vreg[i]) : u32x4{0, 0, 0, 0};   // zero rows keep the MFMA clean
             *reinterpret_cast<u32x4*>(vl + skey * QS_ATT_VSTRIDE + ci * 8) = vz;
         }
         __syncthreads();
@@ -1071,6 +1119,12 @@ __global__ __launch_bounds__(256) void paged_attention_prefill_kernel(
         __syncthreads();   // kl / vl are rewritten by the next chunk
     }
     // ---- results: lane holds rows 4 g4 + reg, columns dt * 16 + c16
+    if constexpr (FP8) {
+#pragma unroll
+        for (int dt = 0; dt < 8; dt++)
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) o[dt][reg] *= v_scale;
+    }
 #pragma unroll
     for (int reg = 0; reg < 4; reg++) {
         const int rr = rbase + 4 * g4 + reg;
@@ -1158,11 +1212,14 @@ __global__ __launch_bounds__(128) void paged_attention_generic_kernel(
 // (next chunk in flight in registers while the current one is accumulated) and thread e then adds the chunk's keys in
 // ascending order: the output sums are those of the kernel above bit for bit; the softmax denominator is summed in a
 // different (fixed) grouping.
+template <typename KVT>   // see paged_attention_kernel ("16-byte piece" below = eight elements: 8 bytes of an fp8 cache)
 __global__ __launch_bounds__(256) void paged_attention_generic_vec_kernel(
-    const f16* __restrict__ q, int64_t q_stride, const f16* __restrict__ key_cache, const f16* __restrict__ value_cache,
+    const f16* __restrict__ q, int64_t q_stride, const KVT* __restrict__ key_cache, const KVT* __restrict__ value_cache,
     const int32_t* __restrict__ block_tables, int max_blocks, const int32_t* __restrict__ ctx_lens,
     const int32_t* __restrict__ q_start, int n_seqs, int nq, int nkv, int d, int block_size, float sm_scale,
-    f16* __restrict__ out, float* __restrict__ ws_o, float* __restrict__ ws_ml) {
+    f16* __restrict__ out, float* __restrict__ ws_o, float* __restrict__ ws_ml, float v_scale) {
+    constexpr bool FP8 = sizeof(KVT) == 1;
+    typedef typename KvRaw<KVT>::type raw_t;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     __shared__ float red[8];
     __shared__ __attribute__((aligned(16))) f16 qrow[256];
@@ -1191,21 +1248,21 @@ __global__ __launch_bounds__(256) void paged_attention_generic_vec_kernel(
     constexpr int PRE = 8;
     const int rg = tid / pieces, vp = tid - rg * pieces;
     const bool pv_on = rg < RG;
-    auto vaddr = [&](int k) -> const f16* {
+    auto vaddr = [&](int k) -> const KVT* {
         const int kc = min(kbase + min(k, nvis - 1), nall - 1);   // clamped: no branch around a load (rows past the end are not used)
         const int64_t slot = (int64_t)bt[kc / block_size] * block_size + kc % block_size;
         return value_cache + (slot * nkv + kvh) * d + vp * 8;
     };
-    u32x4 vpre[PRE];
+    raw_t vpre[PRE];
 #pragma unroll
-    for (int j = 0; j < PRE; j++) vpre[j] = *reinterpret_cast<const u32x4*>(vaddr(rg + RG * j));
+    for (int j = 0; j < PRE; j++) vpre[j] = kv_load8<KVT>(vaddr(rg + RG * j));
     __syncthreads();
     // scores: NK keys per thread and trip -- their table entries first, then every K piece in flight, then the dot products
     // (one key per trip was two dependent round trips per key: 512 keys = four of them per thread)
     constexpr int NK = 4;
     float mx = -__builtin_inff();
     for (int kb = tid; kb < nvis; kb += 256 * NK) {
-        const f16* kp[NK];
+        const KVT* kp[NK];
 #pragma unroll
         for (int i = 0; i < NK; i++) {
             const int kc = min(kbase + min(kb + 256 * i, nvis - 1), nall - 1);   // clamped: rows past the end are loaded, not used
@@ -1216,18 +1273,18 @@ __global__ __launch_bounds__(256) void paged_attention_generic_vec_kernel(
 #pragma unroll
         for (int i = 0; i < NK; i++) acc[i] = 0.0f;
         for (int p0 = 0; p0 < pieces; p0 += 8) {      // up to 8 pieces of each row in flight
-            u32x4 kr[NK][8];
+            raw_t kr[NK][8];
 #pragma unroll
             for (int i = 0; i < NK; i++)
 #pragma unroll
-                for (int j = 0; j < 8; j++) kr[i][j] = *reinterpret_cast<const u32x4*>(kp[i] + min(p0 + j, pieces - 1) * 8);
+                for (int j = 0; j < 8; j++) kr[i][j] = kv_load8<KVT>(kp[i] + min(p0 + j, pieces - 1) * 8);
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 if (p0 + j < pieces) {
                     const f16x8 q8 = *reinterpret_cast<const f16x8*>(qrow + (p0 + j) * 8);
 #pragma unroll
                     for (int i = 0; i < NK; i++) {
-                        const f16x8 k8 = __builtin_bit_cast(f16x8, kr[i][j]);
+                        const f16x8 k8 = __builtin_bit_cast(f16x8, kv_f16x8(kr[i][j]));
 #pragma unroll
                         for (int e = 0; e < 8; e++) acc[i] = __builtin_fmaf(h2f(q8[e]), h2f(k8[e]), acc[i]);
                     }
@@ -1264,8 +1321,8 @@ __global__ __launch_bounds__(256) void paged_attention_generic_vec_kernel(
     float acc[8];
 #pragma unroll
     for (int e = 0; e < 8; e++) acc[e] = 0.0f;
-    auto fma8 = [&](float pk, u32x4 raw) {
-        const f16x8 v8 = __builtin_bit_cast(f16x8, raw);
+    auto fma8 = [&](float pk, raw_t raw) {
+        const f16x8 v8 = __builtin_bit_cast(f16x8, kv_f16x8(raw));
 #pragma unroll
         for (int e = 0; e < 8; e++) acc[e] = __builtin_fmaf(pk, h2f(v8[e]), acc[e]);
     };
@@ -1277,9 +1334,9 @@ __global__ __launch_bounds__(256) void paged_attention_generic_vec_kernel(
             if (k < nvis) fma8(sc[k], vpre[j]);
         }
         for (int k0 = rg + RG * PRE; k0 < nvis; k0 += RG * PRE) {   // long contexts: eight more rows in flight per trip
-            u32x4 vb[PRE];
+            raw_t vb[PRE];
 #pragma unroll
-            for (int j = 0; j < PRE; j++) vb[j] = *reinterpret_cast<const u32x4*>(vaddr(k0 + RG * j));
+            for (int j = 0; j < PRE; j++) vb[j] = kv_load8<KVT>(vaddr(k0 + RG * j));
 #pragma unroll
             for (int j = 0; j < PRE; j++) {
                 const int k = k0 + RG * j;
@@ -1293,6 +1350,7 @@ __global__ __launch_bounds__(256) void paged_attention_generic_vec_kernel(
     if (tid < d) {
         float o = pv_rows > 0 ? pvr[tid] : 0.0f;
         for (int r2 = 1; r2 < pv_rows; r2++) o += pvr[(size_t)r2 * d + tid];
+        if constexpr (FP8) o *= v_scale;
         if (ws_o) {   // partials of split sp: unnormalised output, (row maximum, sum of exponentials)
             const size_t ths = ((size_t)t * nq + h) * S + sp;
             ws_o[ths * d + tid] = o;
@@ -1345,10 +1403,12 @@ static int ilog2_exact(int v) {
     return l;
 }
 
-int paged_attention(const f16* q, int64_t q_stride, const f16* key_cache, const f16* value_cache,
-                    const int32_t* block_tables, int max_blocks, const int32_t* ctx_lens, const int32_t* q_start,
-                    int n_seqs, int max_q_len, int nq, int nkv, int d, int block_size, float sm_scale, int n_splits,
-                    float* ws, f16* out, hipStream_t st) {
+// One dispatch rule for both cache types; sm_scale carries k_scale already (fp8), v_scale goes to the kernels.
+template <typename KVT>
+static int paged_attention_t(const f16* q, int64_t q_stride, const KVT* key_cache, const KVT* value_cache,
+                             const int32_t* block_tables, int max_blocks, const int32_t* ctx_lens, const int32_t* q_start,
+                             int n_seqs, int max_q_len, int nq, int nkv, int d, int block_size, float sm_scale, int n_splits,
+                             float* ws, f16* out, hipStream_t st, float v_scale) {
     // out == nullptr: leave the per-split partials (o, m, l) in the workspace for heads_hadamard_merge
     if (n_seqs == 0) return 0;
     if (nq % nkv) return -1;
@@ -1361,7 +1421,7 @@ int paged_attention(const f16* q, int64_t q_stride, const f16* key_cache, const 
             if (!out && !ws) return -1;
             static bool attr_set = false;
             if (!attr_set) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(paged_attention_generic_vec_kernel),
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(paged_attention_generic_vec_kernel<KVT>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, max_ctx_bytes + 32768 + 16) != hipSuccess)
                     return -8;
                 attr_set = true;
@@ -1376,19 +1436,23 @@ int paged_attention(const f16* q, int64_t q_stride, const f16* key_cache, const 
             const size_t per = (((size_t)max_blocks * block_size + S - 1) / S + 15) & ~(size_t)15;
             if (per * 4 > (size_t)max_ctx_bytes) return -2;
             const size_t lds = ((per * 4 + 15) & ~(size_t)15) + 8192 + 16;
-            hipLaunchKernelGGL(paged_attention_generic_vec_kernel, dim3(n_seqs * max_q_len, nq, S), dim3(256), lds,
+            hipLaunchKernelGGL(paged_attention_generic_vec_kernel<KVT>, dim3(n_seqs * max_q_len, nq, S), dim3(256), lds,
                                st, q, q_stride, key_cache, value_cache, block_tables, max_blocks, ctx_lens, q_start, n_seqs, nq,
-                               nkv, d, block_size, sm_scale, out, ws_o, ws_ml);
+                               nkv, d, block_size, sm_scale, out, ws_o, ws_ml, v_scale);
             if (out && partials)
                 hipLaunchKernelGGL(paged_attention_generic_merge_kernel, dim3((unsigned)(Tm * nq)), dim3(256), 0, st, ws_o, ws_ml, S, d,
                                    out, q_start, n_seqs, nq);
             return 0;
         }
         if (!out) return -1;
-        hipLaunchKernelGGL(paged_attention_generic_kernel, dim3(n_seqs * max_q_len, nq), dim3(128), max_ctx_bytes, st, q,
-                           q_stride, key_cache, value_cache, block_tables, max_blocks, ctx_lens, q_start, n_seqs, nq, nkv,
-                           d, block_size, sm_scale, out);
-        return 0;
+        if constexpr (sizeof(KVT) == 1) {
+            return -6;   // the scalar kernel (odd head sizes, no model uses it) has no fp8 form
+        } else {
+            hipLaunchKernelGGL(paged_attention_generic_kernel, dim3(n_seqs * max_q_len, nq), dim3(128), max_ctx_bytes, st, q,
+                               q_stride, key_cache, value_cache, block_tables, max_blocks, ctx_lens, q_start, n_seqs, nq, nkv,
+                               d, block_size, sm_scale, out);
+            return 0;
+        }
     }
     if (n_splits < 1 || n_splits > QS_ATT_MAXSPLIT) return -3;
     const int bs_log2 = ilog2_exact(block_size), group_log2 = ilog2_exact(nq / nkv);
@@ -1400,9 +1464,9 @@ int paged_attention(const f16* q, int64_t q_stride, const f16* key_cache, const 
         float* fo = ws + QS_ATT_CNT_SLOTS;
         float* fml = fo + Tm * nq * d;
         const size_t flds = (size_t)QS_FA_KEYS * 256 + (size_t)QS_FA_KEYS * QS_ATT_VSTRIDE * 2 + (size_t)4 * 2 * 16 * 72 * 2;
-        hipLaunchKernelGGL(paged_attention_prefill_kernel, dim3(n_seqs, nkv * n_rb64), dim3(256), flds, st, q, q_stride,
+        hipLaunchKernelGGL(paged_attention_prefill_kernel<KVT>, dim3(n_seqs, nkv * n_rb64), dim3(256), flds, st, q, q_stride,
                            key_cache, value_cache, block_tables, max_blocks, ctx_lens, q_start, nq, nkv, bs_log2,
-                           group_log2, sm_scale, n_rb64, fo, fml, out);
+                           group_log2, sm_scale, n_rb64, fo, fml, out, v_scale);
         return 0;
     }
     const int n_rb = ((max_q_len << group_log2) + QS_ATT_MAXR - 1) / QS_ATT_MAXR;
@@ -1431,14 +1495,14 @@ int paged_attention(const f16* q, int64_t q_stride, const f16* key_cache, const 
     do {                                                                                                                   \
         static bool attr_set = false;                                                                                      \
         if (!attr_set) {                                                                                                   \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(paged_attention_waves_kernel<BTV, NWV, FV>),                 \
+            if (hipFuncSetAttribute(reinterpret_cast<const void*>(paged_attention_waves_kernel<BTV, NWV, FV, KVT>),                 \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds) != hipSuccess)                  \
                 return -8;                                                                                                 \
             attr_set = true;                                                                                               \
         }                                                                                                                  \
-        hipLaunchKernelGGL((paged_attention_waves_kernel<BTV, NWV, FV>), dim3(n_seqs, nkv * n_rb, n_splits), dim3(64 * NWV),   \
+        hipLaunchKernelGGL((paged_attention_waves_kernel<BTV, NWV, FV, KVT>), dim3(n_seqs, nkv * n_rb, n_splits), dim3(64 * NWV),   \
                            wlds, st, q, q_stride, key_cache, value_cache, block_tables, max_blocks, ctx_lens, q_start, nq, \
-                           nkv, bs_log2, group_log2, sm_scale, n_splits, n_rb, ws_o, ws_ml);                               \
+                           nkv, bs_log2, group_log2, sm_scale, n_splits, n_rb, ws_o, ws_ml, v_scale);                      \
     } while (0)
         static const int fast_env = QS_DEV_KNOB("QSPEC_ATTN_FAST", 1);
         if (max_blocks <= 128 && bs_log2 >= 4 && fast_env) {   // two uniform table entries per 32-key slice
@@ -1468,15 +1532,28 @@ int paged_attention(const f16* q, int64_t q_stride, const f16* key_cache, const 
     const bool pf = pf_env >= 0 ? pf_env != 0 : (size_t)n_seqs * nkv * n_rb * n_splits <= 256;
     const bool btreg = max_blocks <= 128;
 #define QS_ATT_LAUNCH(PFV, BTV)                                                                                        \
-    hipLaunchKernelGGL((paged_attention_kernel<PFV, BTV>), dim3(n_seqs, nkv * n_rb, n_splits), dim3(256), lds, st, q,     \
+    hipLaunchKernelGGL((paged_attention_kernel<PFV, BTV, KVT>), dim3(n_seqs, nkv * n_rb, n_splits), dim3(256), lds, st, q, \
                        q_stride, key_cache, value_cache, block_tables, max_blocks, ctx_lens, q_start, nq, nkv, bs_log2, \
-                       group_log2, sm_scale, n_splits, n_rb, cnt, ws_o, ws_ml, out, out != nullptr ? 1 : 0)
+                       group_log2, sm_scale, n_splits, n_rb, cnt, ws_o, ws_ml, out, out != nullptr ? 1 : 0, v_scale)
     if (pf && btreg) QS_ATT_LAUNCH(true, true);
     else if (pf) QS_ATT_LAUNCH(true, false);
     else if (btreg) QS_ATT_LAUNCH(false, true);
     else QS_ATT_LAUNCH(false, false);
 #undef QS_ATT_LAUNCH
     return 0;
+}
+
+int paged_attention(const f16* q, int64_t q_stride, const void* key_cache, const void* value_cache,
+                    const int32_t* block_tables, int max_blocks, const int32_t* ctx_lens, const int32_t* q_start,
+                    int n_seqs, int max_q_len, int nq, int nkv, int d, int block_size, float sm_scale, int n_splits,
+                    float* ws, f16* out, hipStream_t st, KvQuant kq) {
+    if (kq.fp8)   // k_scale folds into the softmax scale (an fp32 product), v_scale is applied where a row's output is stored
+        return paged_attention_t<uint8_t>(q, q_stride, (const uint8_t*)key_cache, (const uint8_t*)value_cache, block_tables,
+                                          max_blocks, ctx_lens, q_start, n_seqs, max_q_len, nq, nkv, d, block_size,
+                                          sm_scale * kq.k_scale, n_splits, ws, out, st, kq.v_scale);
+    return paged_attention_t<f16>(q, q_stride, (const f16*)key_cache, (const f16*)value_cache, block_tables, max_blocks,
+                                  ctx_lens, q_start, n_seqs, max_q_len, nq, nkv, d, block_size, sm_scale, n_splits, ws, out,
+                                  st, 1.0f);
 }
 
 }  // namespace qspec

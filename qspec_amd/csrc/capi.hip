@@ -19,6 +19,7 @@ static int fail(const char* fmt, ...) {
     return 1;
 }
 static int finish(const char* op, int rc) {
+    if (rc == -10) return fail("%s: the experimental LDS-DMA QKV variants (QSPEC_SDMA) write fp16 caches only: no fp8 form", op);
     if (rc != 0) return fail("%s: unsupported shape/arguments (code %d)", op, rc);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail("%s: launch failed: %s", op, hipGetErrorString(e));
@@ -49,6 +50,22 @@ struct XpScope {
     XpScope() { g_xp = 1; }
     ~XpScope() { g_xp = 0; }
 };
+
+// The `_kv8` entry points (FP8 e4m3 KV cache) are the base entry points called inside this scope: one body per op, the cache
+// pointers address bytes, and the scales travel to the kernels in g_kq.  Thread-local, set only for the duration of a call.
+static thread_local qspec::KvQuant g_kq;
+struct KvScope {
+    KvScope(float k_scale, float v_scale) {
+        g_kq.fp8 = 1;
+        g_kq.k_scale = k_scale; g_kq.v_scale = v_scale;
+        g_kq.k_inv = 1.0f / k_scale; g_kq.v_inv = 1.0f / v_scale;
+    }
+    ~KvScope() { g_kq = qspec::KvQuant(); }
+};
+#define KV_OP(name) (g_kq.fp8 ? name "_kv8" : name)
+#define KV_SCALES(op)                                                                                         \
+    if (!(k_scale > 0.0f && k_scale < __builtin_inff() && v_scale > 0.0f && v_scale < __builtin_inff()))      \
+        return fail("%s: k_scale=%g, v_scale=%g must be positive and finite", op, (double)k_scale, (double)v_scale)
 
 extern "C" {
 
@@ -259,14 +276,14 @@ int qspec_qkv_rope_linear_w4a16_xp32(const qspec_half* x, const int8_t* wq, cons
                                      int N, int K, const int64_t* positions, const qspec_half* cos_sin_cache,
                                      qspec_half* key_cache, qspec_half* value_cache, const int64_t* slot_mapping,
                                      int num_heads, int num_kv_heads, int head_size, int rot_dim, void* stream) {
-    const char* op = "qspec_qkv_rope_linear_w4a16_xp32";
+    const char* op = KV_OP("qspec_qkv_rope_linear_w4a16_xp32");
     if (M == 0) return 0;
     NONNULL(op, x); NONNULL(op, wq); NONNULL(op, ws); NONNULL(op, qkv); NONNULL(op, positions);
     NONNULL(op, cos_sin_cache); NONNULL(op, key_cache); NONNULL(op, value_cache); NONNULL(op, slot_mapping);
     if ((head_size != 128 && head_size != 64) || rot_dim != head_size) return fail("%s: head_size = rot_dim = 128 or 64 only", op);
     if (!qspec_w4a16_act_layout32_supported(M, N, K))
         return fail("%s: no two-tile streaming form for (M=%d N=%d K=%d)", op, M, N, K);
-    return finish(op, qspec::gemm_w4a16_stream32_qkv_rope(CH(x), wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, ST));
+    return finish(op, qspec::gemm_w4a16_stream32_qkv_rope(CH(x), wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, ST, g_kq));
 }
 int qspec_gate_up_silu_linear_w4a16_xp32(const qspec_half* x, const int8_t* wq, const qspec_half* ws, qspec_half* act, int M,
                                          int intermediate, int K, void* stream) {
@@ -315,18 +332,18 @@ int qspec_rotary_embedding(const int64_t* positions, qspec_half* q, qspec_half* 
 int qspec_reshape_and_cache_flash(const qspec_half* key, const qspec_half* value, qspec_half* key_cache,
                                   qspec_half* value_cache, const int64_t* slot_mapping, int tokens, int num_kv_heads,
                                   int head_size, int64_t key_stride, int64_t value_stride, void* stream) {
-    const char* op = "qspec_reshape_and_cache_flash";
+    const char* op = KV_OP("qspec_reshape_and_cache_flash");
     if (tokens == 0) return 0;
     NONNULL(op, key); NONNULL(op, value); NONNULL(op, key_cache); NONNULL(op, value_cache); NONNULL(op, slot_mapping);
-    return finish(op, qspec::reshape_and_cache_flash(CH(key), CH(value), H(key_cache), H(value_cache), slot_mapping, tokens, num_kv_heads, head_size, key_stride, value_stride, ST));
+    return finish(op, qspec::reshape_and_cache_flash(CH(key), CH(value), H(key_cache), H(value_cache), slot_mapping, tokens, num_kv_heads, head_size, key_stride, value_stride, ST, g_kq));
 }
 int qspec_rope_kv_write(const int64_t* positions, qspec_half* qkv, const qspec_half* cos_sin_cache,
                         qspec_half* key_cache, qspec_half* value_cache, const int64_t* slot_mapping, int tokens,
                         int num_heads, int num_kv_heads, int head_size, int rot_dim, void* stream) {
-    const char* op = "qspec_rope_kv_write";
+    const char* op = KV_OP("qspec_rope_kv_write");
     if (tokens == 0) return 0;
     NONNULL(op, positions); NONNULL(op, qkv); NONNULL(op, cos_sin_cache); NONNULL(op, key_cache); NONNULL(op, value_cache); NONNULL(op, slot_mapping);
-    return finish(op, qspec::rope_kv_write(positions, H(qkv), CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, tokens, num_heads, num_kv_heads, head_size, rot_dim, ST));
+    return finish(op, qspec::rope_kv_write(positions, H(qkv), CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, tokens, num_heads, num_kv_heads, head_size, rot_dim, ST, g_kq));
 }
 size_t qspec_paged_attention_workspace_bytes(int max_tokens, int num_heads, int head_size, int n_splits) {
     return qspec::paged_attention_ws_bytes(max_tokens, num_heads, head_size, n_splits);
@@ -336,14 +353,15 @@ int qspec_paged_attention(const qspec_half* q, int64_t q_stride, const qspec_hal
                           const int32_t* ctx_lens, const int32_t* q_start, int n_seqs, int tokens, int max_q_len,
                           int num_heads, int num_kv_heads, int head_size, int block_size, float sm_scale, int n_splits,
                           void* workspace, qspec_half* out, void* stream) {
-    const char* op = "qspec_paged_attention";
+    const char* op = KV_OP("qspec_paged_attention");
     if (n_seqs == 0 || tokens == 0) return 0;
     NONNULL(op, q); NONNULL(op, key_cache); NONNULL(op, value_cache); NONNULL(op, block_tables); NONNULL(op, ctx_lens);
     NONNULL(op, q_start); NONNULL(op, workspace);   /* out == NULL: partials only, see qspec_heads_hadamard_merged */
     if (head_size != 128 && (head_size > 256 || head_size % 2 || (!out && head_size % 8)))
         return fail("%s: head_size=%d: the matrix-core kernel is built for 128; other even sizes <= 256 run the generic kernel (partials, out = NULL: multiples of 8)", op, head_size);
     if (tokens > n_seqs * max_q_len) return fail("%s: tokens=%d > n_seqs*max_q_len=%d", op, tokens, n_seqs * max_q_len);
-    int rc = qspec::paged_attention(CH(q), q_stride, CH(key_cache), CH(value_cache), block_tables, max_blocks_per_seq, ctx_lens, q_start, n_seqs, max_q_len, num_heads, num_kv_heads, head_size, block_size, sm_scale, n_splits, (float*)workspace, H(out), ST);
+    if (g_kq.fp8 && head_size % 8) return fail("%s: head_size=%d: no fp8 form of the scalar generic kernel (the fp8 cache is read in pieces of eight elements)", op, head_size);
+    int rc = qspec::paged_attention(CH(q), q_stride, CH(key_cache), CH(value_cache), block_tables, max_blocks_per_seq, ctx_lens, q_start, n_seqs, max_q_len, num_heads, num_kv_heads, head_size, block_size, sm_scale, n_splits, (float*)workspace, H(out), ST, g_kq);
     return finish(op, rc);
 }
 int qspec_heads_hadamard_merged(const void* attn_workspace, int max_tokens, int n_splits, qspec_half* out_f16, int8_t* q,
@@ -818,7 +836,7 @@ int qspec_qkv_rope_linear_s4s4(const int8_t* xq, const qspec_half* xs, const int
                                const qspec_half* cos_sin_cache, qspec_half* key_cache, qspec_half* value_cache,
                                const int64_t* slot_mapping, int num_heads, int num_kv_heads, int head_size,
                                int rot_dim, void* stream) {
-    const char* op = "qspec_qkv_rope_linear_s4s4";
+    const char* op = KV_OP("qspec_qkv_rope_linear_s4s4");
     if (M == 0) return 0;
     NONNULL(op, xq); NONNULL(op, xs); NONNULL(op, wq); NONNULL(op, ws); NONNULL(op, qkv); NONNULL(op, positions);
     NONNULL(op, cos_sin_cache); NONNULL(op, key_cache); NONNULL(op, value_cache); NONNULL(op, slot_mapping);
@@ -828,9 +846,9 @@ int qspec_qkv_rope_linear_s4s4(const int8_t* xq, const qspec_half* xs, const int
     if (use_stream() && qspec::gemm_w4a4_stream_supported(M, N, K, false)) {
         qspec::StreamActs x;
         x.xq = xq; x.xs = CH(xs);
-        return finish(op, qspec::gemm_w4a4_stream_qkv_rope(x, wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, ST));
+        return finish(op, qspec::gemm_w4a4_stream_qkv_rope(x, wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, ST, g_kq));
     }
-    return finish(op, qspec::gemm_w4a4_qkv_rope(xq, CH(xs), wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, ST));
+    return finish(op, qspec::gemm_w4a4_qkv_rope(xq, CH(xs), wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, ST, g_kq));
 }
 int qspec_qkv_rope_linear_supported(int w4a4, int M, int N, int K, int head_size) {
     if (head_size == 128) return 1;   // every shape: the streaming kernels, else the first-generation fused kernels
@@ -842,7 +860,8 @@ int qspec_qkv_rope_linear_w4a16(const qspec_half* x, const int8_t* wq, const qsp
                                 qspec_half* key_cache, qspec_half* value_cache, const int64_t* slot_mapping,
                                 int num_heads, int num_kv_heads, int head_size, int rot_dim, void* workspace,
                                 void* stream) {
-    const char* op = "qspec_qkv_rope_linear_w4a16";
+    // (an fp8 call that came in through the _xp entry reports under that entry's name; the fp16 _xp entry keeps reporting as before)
+    const char* op = (g_kq.fp8 && g_xp) ? "qspec_qkv_rope_linear_w4a16_xp_kv8" : KV_OP("qspec_qkv_rope_linear_w4a16");
     if (M == 0) return 0;
     NONNULL(op, x); NONNULL(op, wq); NONNULL(op, ws); NONNULL(op, qkv); NONNULL(op, positions);
     NONNULL(op, cos_sin_cache); NONNULL(op, key_cache); NONNULL(op, value_cache); NONNULL(op, slot_mapping);
@@ -852,8 +871,8 @@ int qspec_qkv_rope_linear_w4a16(const qspec_half* x, const int8_t* wq, const qsp
     if (g_xp && !(use_stream() && qspec::gemm_w4a16_stream_supported(M, N, K) && qspec::gemm_w4a16_xperm_supported(M, K)))
         return fail("%s: no fragment-major form for (M=%d N=%d K=%d)", op, M, N, K);
     if (use_stream() && qspec::gemm_w4a16_stream_supported(M, N, K))
-        return finish(op, qspec::gemm_w4a16_stream_qkv_rope(CH(x), wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, ST, g_xp));
-    return finish(op, qspec::gemm_w4a16_qkv_rope(CH(x), wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, workspace, ST));
+        return finish(op, qspec::gemm_w4a16_stream_qkv_rope(CH(x), wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, ST, g_xp, g_kq));
+    return finish(op, qspec::gemm_w4a16_qkv_rope(CH(x), wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, workspace, ST, g_kq));
 }
 int qspec_qkv_rope_linear_w4a16_xp(const qspec_half* x, const int8_t* wq, const qspec_half* ws, qspec_half* qkv, int M,
                                    int N, int K, const int64_t* positions, const qspec_half* cos_sin_cache,
@@ -941,7 +960,7 @@ int qspec_ln_qkv_rope_linear_s4s4(const qspec_half* hidden_in, const qspec_half*
                                   qspec_half* key_cache, qspec_half* value_cache, const int64_t* slot_mapping,
                                   int num_heads, int num_kv_heads, int head_size, int rot_dim, void* sync_workspace,
                                   void* stream) {
-    const char* op = "qspec_ln_qkv_rope_linear_s4s4";
+    const char* op = KV_OP("qspec_ln_qkv_rope_linear_s4s4");
     if (M == 0) return 0;
     NONNULL(op, hidden_in); NONNULL(op, wq); NONNULL(op, ws); NONNULL(op, qkv); NONNULL(op, positions);
     NONNULL(op, cos_sin_cache); NONNULL(op, key_cache); NONNULL(op, value_cache); NONNULL(op, slot_mapping);
@@ -952,7 +971,7 @@ int qspec_ln_qkv_rope_linear_s4s4(const qspec_half* hidden_in, const qspec_half*
     qspec::StreamActs x;
     x.hidden_in = CH(hidden_in); x.delta = CH(delta); x.hidden_out = H(hidden_out); x.eps = eps;
     x.sync = reinterpret_cast<int*>(sync_workspace);
-    return finish(op, qspec::gemm_w4a4_stream_qkv_rope(x, wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, ST));
+    return finish(op, qspec::gemm_w4a4_stream_qkv_rope(x, wq, CH(ws), H(qkv), M, N, K, positions, CH(cos_sin_cache), H(key_cache), H(value_cache), slot_mapping, num_heads, num_kv_heads, head_size, rot_dim, ST, g_kq));
 }
 int qspec_ln_gate_up_silu_linear_s4s4(const qspec_half* hidden_in, const qspec_half* delta, qspec_half* hidden_out,
                                       float eps, const int8_t* wq, const qspec_half* ws, qspec_half* act, int M,
@@ -1055,5 +1074,101 @@ int qspec_prefetch_tiles(const void* p, size_t tile_bytes, int first_tile, int n
 }
 #endif
 int qspec_ln_linear_s4s4_supported(int M, int N, int K) { return qspec::gemm_w4a4_stream_supported(M, N, K, true) ? 1 : 0; }
+
+/* ---- FP8 (e4m3fn) KV cache: the entries above inside a KvScope (qspec_hip.h, "FP8 KV cache") ---- */
+int qspec_reshape_and_cache_flash_kv8(const qspec_half* key, const qspec_half* value, uint8_t* key_cache,
+                                      uint8_t* value_cache, float k_scale, float v_scale, const int64_t* slot_mapping,
+                                      int tokens, int num_kv_heads, int head_size, int64_t key_stride,
+                                      int64_t value_stride, void* stream) {
+    KV_SCALES("qspec_reshape_and_cache_flash_kv8");
+    KvScope kv(k_scale, v_scale);
+    return qspec_reshape_and_cache_flash(key, value, reinterpret_cast<qspec_half*>(key_cache),
+                                         reinterpret_cast<qspec_half*>(value_cache), slot_mapping, tokens,
+                                         num_kv_heads, head_size, key_stride, value_stride, stream);
+}
+int qspec_rope_kv_write_kv8(const int64_t* positions, qspec_half* qkv, const qspec_half* cos_sin_cache,
+                            uint8_t* key_cache, uint8_t* value_cache, float k_scale, float v_scale,
+                            const int64_t* slot_mapping, int tokens, int num_heads, int num_kv_heads, int head_size,
+                            int rot_dim, void* stream) {
+    KV_SCALES("qspec_rope_kv_write_kv8");
+    KvScope kv(k_scale, v_scale);
+    return qspec_rope_kv_write(positions, qkv, cos_sin_cache, reinterpret_cast<qspec_half*>(key_cache),
+                               reinterpret_cast<qspec_half*>(value_cache), slot_mapping, tokens, num_heads,
+                               num_kv_heads, head_size, rot_dim, stream);
+}
+int qspec_paged_attention_kv8(const qspec_half* q, int64_t q_stride, const uint8_t* key_cache,
+                              const uint8_t* value_cache, float k_scale, float v_scale, const int32_t* block_tables,
+                              int max_blocks_per_seq, const int32_t* ctx_lens, const int32_t* q_start, int n_seqs,
+                              int tokens, int max_q_len, int num_heads, int num_kv_heads, int head_size,
+                              int block_size, float sm_scale, int n_splits, void* workspace, qspec_half* out,
+                              void* stream) {
+    KV_SCALES("qspec_paged_attention_kv8");
+    KvScope kv(k_scale, v_scale);
+    return qspec_paged_attention(q, q_stride, reinterpret_cast<const qspec_half*>(key_cache),
+                                 reinterpret_cast<const qspec_half*>(value_cache), block_tables, max_blocks_per_seq,
+                                 ctx_lens, q_start, n_seqs, tokens, max_q_len, num_heads, num_kv_heads, head_size,
+                                 block_size, sm_scale, n_splits, workspace, out, stream);
+}
+int qspec_qkv_rope_linear_s4s4_kv8(const int8_t* xq, const qspec_half* xs, const int8_t* wq, const qspec_half* ws,
+                                   qspec_half* qkv, int M, int N, int K, const int64_t* positions,
+                                   const qspec_half* cos_sin_cache, uint8_t* key_cache, uint8_t* value_cache,
+                                   float k_scale, float v_scale, const int64_t* slot_mapping, int num_heads,
+                                   int num_kv_heads, int head_size, int rot_dim, void* stream) {
+    KV_SCALES("qspec_qkv_rope_linear_s4s4_kv8");
+    KvScope kv(k_scale, v_scale);
+    return qspec_qkv_rope_linear_s4s4(xq, xs, wq, ws, qkv, M, N, K, positions, cos_sin_cache,
+                                      reinterpret_cast<qspec_half*>(key_cache),
+                                      reinterpret_cast<qspec_half*>(value_cache), slot_mapping, num_heads,
+                                      num_kv_heads, head_size, rot_dim, stream);
+}
+int qspec_qkv_rope_linear_w4a16_kv8(const qspec_half* x, const int8_t* wq, const qspec_half* ws, qspec_half* qkv,
+                                    int M, int N, int K, const int64_t* positions, const qspec_half* cos_sin_cache,
+                                    uint8_t* key_cache, uint8_t* value_cache, float k_scale, float v_scale,
+                                    const int64_t* slot_mapping, int num_heads, int num_kv_heads, int head_size,
+                                    int rot_dim, void* workspace, void* stream) {
+    KV_SCALES("qspec_qkv_rope_linear_w4a16_kv8");
+    KvScope kv(k_scale, v_scale);
+    return qspec_qkv_rope_linear_w4a16(x, wq, ws, qkv, M, N, K, positions, cos_sin_cache,
+                                       reinterpret_cast<qspec_half*>(key_cache),
+                                       reinterpret_cast<qspec_half*>(value_cache), slot_mapping, num_heads,
+                                       num_kv_heads, head_size, rot_dim, workspace, stream);
+}
+int qspec_qkv_rope_linear_w4a16_xp_kv8(const qspec_half* x, const int8_t* wq, const qspec_half* ws, qspec_half* qkv,
+                                       int M, int N, int K, const int64_t* positions, const qspec_half* cos_sin_cache,
+                                       uint8_t* key_cache, uint8_t* value_cache, float k_scale, float v_scale,
+                                       const int64_t* slot_mapping, int num_heads, int num_kv_heads, int head_size,
+                                       int rot_dim, void* workspace, void* stream) {
+    KV_SCALES("qspec_qkv_rope_linear_w4a16_xp_kv8");
+    KvScope kv(k_scale, v_scale);
+    return qspec_qkv_rope_linear_w4a16_xp(x, wq, ws, qkv, M, N, K, positions, cos_sin_cache,
+                                          reinterpret_cast<qspec_half*>(key_cache),
+                                          reinterpret_cast<qspec_half*>(value_cache), slot_mapping, num_heads,
+                                          num_kv_heads, head_size, rot_dim, workspace, stream);
+}
+int qspec_qkv_rope_linear_w4a16_xp32_kv8(const qspec_half* x, const int8_t* wq, const qspec_half* ws, qspec_half* qkv,
+                                         int M, int N, int K, const int64_t* positions,
+                                         const qspec_half* cos_sin_cache, uint8_t* key_cache, uint8_t* value_cache,
+                                         float k_scale, float v_scale, const int64_t* slot_mapping, int num_heads,
+                                         int num_kv_heads, int head_size, int rot_dim, void* stream) {
+    KV_SCALES("qspec_qkv_rope_linear_w4a16_xp32_kv8");
+    KvScope kv(k_scale, v_scale);
+    return qspec_qkv_rope_linear_w4a16_xp32(x, wq, ws, qkv, M, N, K, positions, cos_sin_cache,
+                                            reinterpret_cast<qspec_half*>(key_cache),
+                                            reinterpret_cast<qspec_half*>(value_cache), slot_mapping, num_heads,
+                                            num_kv_heads, head_size, rot_dim, stream);
+}
+int qspec_ln_qkv_rope_linear_s4s4_kv8(const qspec_half* hidden_in, const qspec_half* delta, qspec_half* hidden_out,
+                                      float eps, const int8_t* wq, const qspec_half* ws, qspec_half* qkv, int M,
+                                      int N, int K, const int64_t* positions, const qspec_half* cos_sin_cache,
+                                      uint8_t* key_cache, uint8_t* value_cache, float k_scale, float v_scale,
+                                      const int64_t* slot_mapping, int num_heads, int num_kv_heads, int head_size,
+                                      int rot_dim, void* sync_workspace, void* stream) {
+    KV_SCALES("qspec_ln_qkv_rope_linear_s4s4_kv8");
+    KvScope kv(k_scale, v_scale);
+    return qspec_ln_qkv_rope_linear_s4s4(hidden_in, delta, hidden_out, eps, wq, ws, qkv, M, N, K, positions,
+                                         cos_sin_cache, reinterpret_cast<qspec_half*>(key_cache),
+                                         reinterpret_cast<qspec_half*>(value_cache), slot_mapping, num_heads,
+                                         num_kv_heads, head_size, rot_dim, sync_workspace, stream);
+}
 
 }  // extern "C"

@@ -43,6 +43,43 @@ __device__ __forceinline__ f16 f2h(float f) {
     asm("" : "+v"(f));
     return (f16)f;
 }
+// FP8 KV cache (include/qspec_hip.h, "FP8 KV cache"): OCP e4m3fn bytes, gfx950's native conversions.
+// Write: e4m3_rne(clamp(f(x) * inv, -448, 448)).  The clamp is two compare-and-selects in fp32 in front of the convert (a
+// NaN passes through both and converts to the e4m3 NaN), so the byte never depends on the hardware's overflow mode.
+__device__ __forceinline__ uint8_t f2e4m3(float x) {
+    x = x < -448.0f ? -448.0f : x;
+    x = x > 448.0f ? 448.0f : x;
+    return (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(x, x, 0, false) & 0xff);
+}
+__device__ __forceinline__ u32 f2e4m3_x4(float a, float b, float c, float d) {   // bytes a, b, c, d in memory order
+    a = a < -448.0f ? -448.0f : a; a = a > 448.0f ? 448.0f : a;
+    b = b < -448.0f ? -448.0f : b; b = b > 448.0f ? 448.0f : b;
+    c = c < -448.0f ? -448.0f : c; c = c > 448.0f ? 448.0f : c;
+    d = d < -448.0f ? -448.0f : d; d = d > 448.0f ? 448.0f : d;
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+    return (u32)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+}
+// Read: eight e4m3 bytes -> eight halves, exact (every e4m3 value is an fp16 value): four v_cvt_scalef32_pk_f16_fp8 with
+// scale 1.  The tensor's scale is applied elsewhere (k: in the softmax scale, v: where an output row is stored).
+__device__ __forceinline__ u32x4 e4m3x8_to_f16x8(u32x2 r) {
+    u32x4 o;
+    o[0] = __builtin_bit_cast(u32, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)r[0], 1.0f, false));
+    o[1] = __builtin_bit_cast(u32, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)r[0], 1.0f, true));
+    o[2] = __builtin_bit_cast(u32, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)r[1], 1.0f, false));
+    o[3] = __builtin_bit_cast(u32, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)r[1], 1.0f, true));
+    return o;
+}
+__device__ __forceinline__ float e4m3_to_f32(uint8_t b) { return __builtin_amdgcn_cvt_f32_fp8((int)b, 0); }
+// K / V bytes as they sit in registers between the load and the first use: 16 B (eight halves) of an fp16 cache,
+// 8 B (eight e4m3) of an fp8 cache.  kv_f16x8() is the identity for fp16.
+template <typename KVT> struct KvRaw { typedef u32x4 type; };
+template <> struct KvRaw<uint8_t> { typedef u32x2 type; };
+template <typename KVT>
+__device__ __forceinline__ typename KvRaw<KVT>::type kv_load8(const KVT* p) {
+    return *reinterpret_cast<const typename KvRaw<KVT>::type*>(p);
+}
+__device__ __forceinline__ u32x4 kv_f16x8(u32x4 r) { return r; }
+__device__ __forceinline__ u32x4 kv_f16x8(u32x2 r) { return e4m3x8_to_f16x8(r); }
 __device__ __forceinline__ f16 u2h(uint16_t u) { return __builtin_bit_cast(f16, u); }
 __device__ __forceinline__ uint16_t h2u(f16 h) { return __builtin_bit_cast(uint16_t, h); }
 

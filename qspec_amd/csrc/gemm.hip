@@ -65,6 +65,8 @@ struct EpiArgs {
     int tb0;                    // first tile of this launch (tensor-parallel column shards launch a sub-range)
     int64_t ldw;                // bytes between packed weight rows (0 = K/2): K-sliced views of the shared buffer
     int64_t ldx;                // halves between fp16 activation rows (0 = K)
+    int kv8;                    // EPI_QKV: the caches hold e4m3 bytes (the `_kv8` entries); k_inv / v_inv = 1.0f / scale
+    float k_inv, v_inv;
 };
 
 template <int EPI>
@@ -112,7 +114,9 @@ __device__ __forceinline__ void epilogue_store(f16 hv, bool valid, int m, int c,
             const bool is_k = head < ea.nq + ea.nkv;
             const int kvh = is_k ? head - ea.nq : head - ea.nq - ea.nkv;
             f16* cache = is_k ? ea.key_cache : ea.value_cache;
-            cache[(slot * ea.nkv + kvh) * 128 + (c >> 3) * 64 + o] = res;
+            const int64_t ci = (slot * ea.nkv + kvh) * 128 + (c >> 3) * 64 + o;
+            if (ea.kv8) reinterpret_cast<uint8_t*>(cache)[ci] = f2e4m3(h2f(res) * (is_k ? ea.k_inv : ea.v_inv));
+            else cache[ci] = res;
         }
     }
 }
@@ -237,10 +241,11 @@ static int check_qkv(int N, int K, int nq, int nkv, int d, int rot_dim) {
 
 int gemm_w4a4_qkv_rope(const int8_t* xq, const f16* xs, const int8_t* wq, const f16* ws, f16* qkv, int M, int N, int K,
                        const int64_t* positions, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                       const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st) {
+                       const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st, KvQuant kq) {
     if (M == 0) return 0;
     if (check_qkv(N, K, nq, nkv, d, rot_dim)) return -1;
     EpiArgs ea{positions, cos_sin_cache, key_cache, value_cache, slot_mapping, nq, nkv, 0};
+    ea.kv8 = kq.fp8; ea.k_inv = kq.k_inv; ea.v_inv = kq.v_inv;
     return launch_w4a4<EPI_QKV>(xq, xs, wq, ws, nullptr, qkv, M, N, K, ea, st);
 }
 
@@ -593,10 +598,11 @@ int gemm_w4a16_strided_raw(const f16* x, int64_t ldx, const int8_t* wq, int64_t 
 
 int gemm_w4a16_qkv_rope(const f16* x, const int8_t* wq, const f16* ws, f16* qkv, int M, int N, int K,
                         const int64_t* positions, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                        const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, void* wsp, hipStream_t st) {
+                        const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, void* wsp, hipStream_t st, KvQuant kq) {
     if (M == 0) return 0;
     if (check_qkv(N, K, nq, nkv, d, rot_dim)) return -1;
     EpiArgs ea{positions, cos_sin_cache, key_cache, value_cache, slot_mapping, nq, nkv, 0};
+    ea.kv8 = kq.fp8; ea.k_inv = kq.k_inv; ea.v_inv = kq.v_inv;
     return launch_w4a16<EPI_QKV>(x, wq, ws, nullptr, qkv, M, N, K, ea, wsp, st);
 }
 

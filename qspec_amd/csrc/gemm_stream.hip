@@ -89,7 +89,17 @@ struct StreamArgs {
     const int64_t* slot_mapping;
     int nq, nkv, I;
     int hdl = 7;   // SEPI_QKV: log2(head size), 7 or 6
+    int kv8 = 0;   // SEPI_QKV: the caches hold e4m3 bytes (the `_kv8` entries); k_inv / v_inv = 1.0f / scale
+    float k_inv = 1.0f, v_inv = 1.0f;
 };
+
+// The cache store of the SEPI_QKV epilogues: the fp16 value, or its e4m3 byte at the same element position (uniform branch:
+// one launch form for both cache types; reshape_and_cache_flash(..., "fp8", k_scale, v_scale)).
+__device__ __forceinline__ void kv_cache_store(const StreamArgs& a, bool is_k, int64_t idx, f16 res) {
+    f16* cache = is_k ? a.key_cache : a.value_cache;
+    if (a.kv8) reinterpret_cast<uint8_t*>(cache)[idx] = f2e4m3(h2f(res) * (is_k ? a.k_inv : a.v_inv));
+    else cache[idx] = res;
+}
 
 __device__ __forceinline__ i32x4 widen16(u32 p0, u32 p1) {
     return i32x4{(int)((p0 << 4) & 0xF0F0F0F0u), (int)(p0 & 0xF0F0F0F0u), (int)((p1 << 4) & 0xF0F0F0F0u),
@@ -732,8 +742,7 @@ __global__ __launch_bounds__(NW * 64 + (pro_split<PRO>() ? 256 : 0) + (DMA > 0 ?
         if (head >= a.nq && slot_m >= 0) {
             const bool is_k = head < a.nq + a.nkv;
             const int kvh = is_k ? head - a.nq : head - a.nq - a.nkv;
-            f16* cache = is_k ? a.key_cache : a.value_cache;
-            cache[((slot_m * a.nkv + kvh) << a.hdl) + ((c >> 3) << (a.hdl - 1)) + o] = res;
+            kv_cache_store(a, is_k, ((slot_m * a.nkv + kvh) << a.hdl) + ((c >> 3) << (a.hdl - 1)) + o, res);
         }
     };
 
@@ -1416,8 +1425,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_w4a16_stream_kernel(StreamArgs a
         if (head >= a.nq && slot_m >= 0) {
             const bool is_k = head < a.nq + a.nkv;
             const int kvh = is_k ? head - a.nq : head - a.nq - a.nkv;
-            f16* cache = is_k ? a.key_cache : a.value_cache;
-            cache[((slot_m * a.nkv + kvh) << a.hdl) + ((c >> 3) << (a.hdl - 1)) + o] = res;
+            kv_cache_store(a, is_k, ((slot_m * a.nkv + kvh) << a.hdl) + ((c >> 3) << (a.hdl - 1)) + o, res);
         }
     };
     for (int q = 0; q < my_tiles - 1; q++) {
@@ -2300,8 +2308,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_w4a16_stream2_kernel(StreamArgs 
         if (head >= a.nq && slot_m >= 0) {
             const bool is_k = head < a.nq + a.nkv;
             const int kvh = is_k ? head - a.nq : head - a.nq - a.nkv;
-            f16* cache = is_k ? a.key_cache : a.value_cache;
-            cache[((slot_m * a.nkv + kvh) << a.hdl) + ((c >> 3) << (a.hdl - 1)) + o] = res;
+            kv_cache_store(a, is_k, ((slot_m * a.nkv + kvh) << a.hdl) + ((c >> 3) << (a.hdl - 1)) + o, res);
         }
     };
     // the (pass, tile) units of this workgroup in order; the weights of unit q + 1 are requested behind the use of unit q's
@@ -2418,9 +2425,10 @@ int gemm_w4a16_stream32(const f16* x, const int8_t* wq, const f16* ws, f16* out,
 }
 int gemm_w4a16_stream32_qkv_rope(const f16* x, const int8_t* wq, const f16* ws, f16* qkv, int M, int N, int K,
                                  const int64_t* positions, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                                 const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st) {
+                                 const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st, KvQuant kq) {
     if ((d != 128 && d != 64) || rot_dim != d || N != (nq + 2 * nkv) * d) return -1;
     StreamArgs a{};
+    a.kv8 = kq.fp8; a.k_inv = kq.k_inv; a.v_inv = kq.v_inv;
     a.hdl = d == 64 ? 6 : 7;
     a.x = x; a.wq = reinterpret_cast<const uint8_t*>(wq); a.ws = ws; a.out = qkv; a.M = M; a.N = N; a.K = K;
     a.ntiles = N / 16; a.positions = positions; a.cos_sin_cache = cos_sin_cache; a.key_cache = key_cache;
@@ -2568,10 +2576,12 @@ static int qkv_level_workgroups(int nq, int nkv, int N) {
 
 int gemm_w4a16_stream_qkv_rope(const f16* x, const int8_t* wq, const f16* ws, f16* qkv, int M, int N, int K,
                                const int64_t* positions, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                               const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st, int xperm) {
+                               const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st, int xperm,
+                               KvQuant kq) {
     if ((d != 128 && d != 64) || rot_dim != d || N != (nq + 2 * nkv) * d || !gemm_w4a16_stream_supported(M, N, K)) return -1;
     if (xperm && !gemm_w4a16_xperm_supported(M, K)) return -1;
     StreamArgs a{};
+    a.kv8 = kq.fp8; a.k_inv = kq.k_inv; a.v_inv = kq.v_inv;
     a.xperm = xperm;
     a.hdl = d == 64 ? 6 : 7;
     a.x = x; a.wq = reinterpret_cast<const uint8_t*>(wq); a.ws = ws; a.out = qkv; a.M = M; a.N = N; a.K = K;
@@ -2661,16 +2671,18 @@ int gemm_w4a4_stream_residual_hq(const f16* x16, const float* part_amax, int npa
 }
 int gemm_w4a4_stream_qkv_rope(const StreamActs& x, const int8_t* wq, const f16* ws, f16* qkv, int M, int N, int K,
                               const int64_t* positions, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                              const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st) {
+                              const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st, KvQuant kq) {
     if ((d != 128 && d != 64) || rot_dim != d || N != (nq + 2 * nkv) * d) return -1;
     if (!gemm_w4a4_stream_supported(M, N, K, x.hidden_in != nullptr)) return -1;
     StreamArgs a{};
+    a.kv8 = kq.fp8; a.k_inv = kq.k_inv; a.v_inv = kq.v_inv;
     a.hdl = d == 64 ? 6 : 7;
     a.xq = x.xq; a.xs = x.xs; a.hidden_in = x.hidden_in; a.delta = x.delta; a.hidden_out = x.hidden_out; a.eps = x.eps; a.sync = x.sync;
     a.wq = reinterpret_cast<const uint8_t*>(wq); a.ws = ws; a.out = qkv; a.M = M; a.N = N; a.K = K; a.ntiles = N / 16;
     a.positions = positions; a.cos_sin_cache = cos_sin_cache; a.key_cache = key_cache; a.value_cache = value_cache;
     a.slot_mapping = slot_mapping; a.nq = nq; a.nkv = nkv;
 #ifdef QS_EXPERIMENTAL
+    if (kq.fp8 && sdma_on<SEPI_QKV>()) return -10;   // the LDS-DMA variants write fp16 caches only (capi.hip names the reason)
     if (!sdma_on<SEPI_QKV>()) {   // (the LDS-DMA forms keep the classic tiles)
         if (const int L = d == 128 ? qkv_level_workgroups(nq, nkv, N) : 0) {
             a.I = L;

@@ -17,6 +17,15 @@
 namespace qspec {
 typedef _Float16 f16;
 
+// FP8 (e4m3fn) KV cache, the `_kv8` entries of the C ABI: the cache pointers of the functions below address bytes instead of
+// halves (same element positions), a writer stores e4m3_rne(clamp(f(x) * inv, -448, 448)), a reader folds k_scale into the
+// softmax scale and multiplies the stored output by v_scale.  Default-constructed = the fp16 cache.
+struct KvQuant {
+    int fp8 = 0;
+    float k_scale = 1.0f, v_scale = 1.0f;   // readers
+    float k_inv = 1.0f, v_inv = 1.0f;       // writers: 1.0f / scale, computed once on the host in fp32
+};
+
 // norm_quant.hip
 int ln_quant_i4(const f16* x, const f16* delta, f16* hidden_out, int8_t* q, f16* scale, f16* isum, float eps, int T,
                 int H, hipStream_t st);
@@ -46,7 +55,7 @@ int gemm_w4a16_stream32_partial(const f16* x, const int8_t* wq, float* part, int
 int gemm_w4a16_stream32(const f16* x, const int8_t* wq, const f16* ws, f16* out, int M, int N, int K, hipStream_t st);
 int gemm_w4a16_stream32_qkv_rope(const f16* x, const int8_t* wq, const f16* ws, f16* qkv, int M, int N, int K,
                                  const int64_t* positions, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                                 const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st);
+                                 const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st, KvQuant kq = KvQuant());
 int gemm_w4a16_stream32_gate_up_silu(const f16* x, const int8_t* wq, const f16* ws, f16* act, int M, int I, int K, hipStream_t st);
 int silu_mul_hadamard(const f16* gate_up, const f16* hadK, f16* out_f16, int8_t* q, f16* scale, float had_scale,
                       float clip, int T, int I, int K, int pre_activated, void* xws, hipStream_t st, int xp = 0);
@@ -60,10 +69,10 @@ int gemm_w4a16(const f16* x, const int8_t* wq, const f16* ws, const f16* bias, f
                void* wsp, hipStream_t st);
 int gemm_w4a4_qkv_rope(const int8_t* xq, const f16* xs, const int8_t* wq, const f16* ws, f16* qkv, int M, int N, int K,
                        const int64_t* positions, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                       const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st);
+                       const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st, KvQuant kq = KvQuant());
 int gemm_w4a16_qkv_rope(const f16* x, const int8_t* wq, const f16* ws, f16* qkv, int M, int N, int K,
                         const int64_t* positions, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                        const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, void* wsp, hipStream_t st);
+                        const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, void* wsp, hipStream_t st, KvQuant kq = KvQuant());
 int gemm_w4a4_gate_up_silu(const int8_t* xq, const f16* xs, const int8_t* wq, const f16* ws, f16* act, int M, int I,
                            int K, hipStream_t st);
 int gemm_w4a16_gate_up_silu(const f16* x, const int8_t* wq, const f16* ws, f16* act, int M, int I, int K, int ch0,
@@ -107,7 +116,7 @@ int heads_hadamard_merge_spread(const float* ws, int max_tokens, int n_splits, f
                                 int T, int heads, int d, hipStream_t st);
 int gemm_w4a4_stream_qkv_rope(const StreamActs& x, const int8_t* wq, const f16* ws, f16* qkv, int M, int N, int K,
                               const int64_t* positions, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                              const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st);
+                              const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st, KvQuant kq = KvQuant());
 int gemm_w4a4_stream_gate_up_silu(const StreamActs& x, const int8_t* wq, const f16* ws, f16* act, int M, int I, int K,
                                   hipStream_t st);
 
@@ -122,7 +131,8 @@ int gemm_w4a16_stream_partial(const f16* x, int64_t ldx, const int8_t* wq, int64
 int gemm_w4a16_partial_finish(const float* part, const f16* ws, f16* out, int M, int N, int S, hipStream_t st);
 int gemm_w4a16_stream_qkv_rope(const f16* x, const int8_t* wq, const f16* ws, f16* qkv, int M, int N, int K,
                                const int64_t* positions, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                               const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st, int xperm = 0);
+                               const int64_t* slot_mapping, int nq, int nkv, int d, int rot_dim, hipStream_t st, int xperm = 0,
+                               KvQuant kq = KvQuant());
 int gemm_w4a16_stream_gate_up_silu(const f16* x, const int8_t* wq, const f16* ws, f16* act, int M, int I, int K, int ch0,
                                    int nch, hipStream_t st, int xperm = 0);
 
@@ -146,17 +156,17 @@ int prefetch_tiles(const void* p, size_t tile_bytes, int first_tile, int ntiles,
 #endif
 
 // attention.hip
-int rope_kv_write(const int64_t* positions, f16* qkv, const f16* cos_sin_cache, f16* key_cache, f16* value_cache,
-                  const int64_t* slot_mapping, int T, int nq, int nkv, int d, int rot_dim, hipStream_t st);
+int rope_kv_write(const int64_t* positions, f16* qkv, const f16* cos_sin_cache, void* key_cache, void* value_cache,
+                  const int64_t* slot_mapping, int T, int nq, int nkv, int d, int rot_dim, hipStream_t st, KvQuant kq = KvQuant());
 int rotary_embedding(const int64_t* positions, f16* q, f16* k, const f16* cos_sin_cache, int T, int nq, int nkv,
                      int d, int rot_dim, int64_t q_stride, int64_t k_stride, hipStream_t st);
-int reshape_and_cache_flash(const f16* key, const f16* value, f16* key_cache, f16* value_cache,
+int reshape_and_cache_flash(const f16* key, const f16* value, void* key_cache, void* value_cache,
                             const int64_t* slot_mapping, int T, int nkv, int d, int64_t k_stride, int64_t v_stride,
-                            hipStream_t st);
-int paged_attention(const f16* q, int64_t q_stride, const f16* key_cache, const f16* value_cache,
+                            hipStream_t st, KvQuant kq = KvQuant());
+int paged_attention(const f16* q, int64_t q_stride, const void* key_cache, const void* value_cache,
                     const int32_t* block_tables, int max_blocks, const int32_t* ctx_lens, const int32_t* q_start,
                     int n_seqs, int max_q_len, int nq, int nkv, int d, int block_size, float sm_scale, int n_splits,
-                    float* ws, f16* out, hipStream_t st);
+                    float* ws, f16* out, hipStream_t st, KvQuant kq = KvQuant());
 size_t paged_attention_ws_bytes(int T, int nq, int d, int n_splits);
 size_t paged_attention_ws_o_offset();
 int paged_attention_generic_splits(int n_splits);   // head sizes other than 128: the splits actually used for a caller's n_splits

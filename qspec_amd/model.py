@@ -226,7 +226,23 @@ class QuarotLlamaForCausalLM:
     MERGE_IN_HADAMARD = True   # False: the attention kernel merges its context splits itself (ticket + fences)
     DOWN_K_SLICES = __import__("os").environ.get("QSPEC_DOWN_K_SLICES", "1") != "0"   # draft down_proj at 17..32 tokens as K slices
 
-    def _attention_hadamard(self, qkv, row, kc, vc, md, T, s, attn, q1, sc, had, xp=False):
+    # FP8 KV cache: per-layer (k_scale, v_scale) read from the checkpoint (model.layers.{i}.self_attn.k_scale / .v_scale);
+    # None = 1.0 everywhere.  Only consulted when the cache tensors are bytes.  A caller with scales of its own (the engine's
+    # `kv_scales`) passes them to forward(): several engines share one model, so nobody writes them here.
+    kv_scales = None
+
+    def _kv_kw(self, li, kc, kv_scales=None):
+        """Keywords of the ops that touch the cache of layer li: nothing for an fp16 cache (the calls are exactly those of a
+        model that knows no fp8), the layer's scales for an fp8 cache -- the caller's, else the checkpoint's, else 1.0.  No
+        launch-form decision depends on it."""
+        if kc.dtype == torch.float16:
+            return {}
+        if kv_scales is None:
+            kv_scales = self.kv_scales
+        ks, vs = kv_scales[li] if kv_scales is not None else (1.0, 1.0)
+        return {"k_scale": float(ks), "v_scale": float(vs)}
+
+    def _attention_hadamard(self, qkv, row, kc, vc, md, T, s, attn, q1, sc, had, xp=False, kvs=None):
         """Attention + head Hadamard (+ quant when q1 is given, else fp16 into `had`) (quarot_llama.py:213-238).
         For 32 / 64 heads of 128 the split merge of the attention kernel runs at the head of the Hadamard launch."""
         cfg = self.config
@@ -239,7 +255,7 @@ class QuarotLlamaForCausalLM:
         mix_merged = (self.MERGE_IN_HADAMARD and self.head_had_K > 1 and md.n_splits <= 64
                       and ops.heads_hadamard_mix_merged_spread_supported(T, nh, cfg.head_dim, self.head_had_K))
         ops.paged_attention(qkv, row, kc, vc, md.block_tables, md.ctx_lens, md.q_start, T, md.max_q_len, nh,
-                            self.sm_scale, md.n_splits, s.attn_ws, None if (merged or mix_merged) else attn)
+                            self.sm_scale, md.n_splits, s.attn_ws, None if (merged or mix_merged) else attn, **(kvs or {}))
         if self.head_had_K > 1:
             buf = had if had is not None else s.act_buffer_had[:T]
             if mix_merged:
@@ -263,7 +279,7 @@ class QuarotLlamaForCausalLM:
 
     # ------------------------------------------------------------------ fused product path
     def forward(self, input_ids, positions, kv_caches, attn_metadata: AttentionMetadata, scratch: Scratch,
-                w4a4: bool = False, embedded: bool = False, **kwargs):
+                w4a4: bool = False, embedded: bool = False, kv_scales=None, **kwargs):
         """LlamaModel.forward (quarot_llama.py:484-535) + final norm; returns the normed hidden states [T,H].
         embedded: scratch.hidden[:T] already holds embed_tokens[input_ids] (the engine's bookkeeping launches write it:
         ops.spec_prepare_draft / spec_advance_draft / spec_prepare_verify with embed=...)."""
@@ -324,18 +340,19 @@ class QuarotLlamaForCausalLM:
                   if (w4a4 and fuse and not ln_fused and s.down_ipart is not None and self.DOWN_K_SLICES) else 0)
         for li, layer in enumerate(self.layers):
             kc, vc = kv_caches[li]
+            kvs = self._kv_kw(li, kc, kv_scales)
             qkv_w, qkv_s = layer.qkv_proj.weight, layer.qkv_proj._scales()
             gu_w, gu_s = layer.gate_up.weight, layer.gate_up._scales()
             if ln_fused:
                 # 7 launches per layer; the residual stream is updated in the o_proj / down_proj epilogues
                 # (hidden = residual + proj_out, :380,390), the norms read it in the qkv / gate_up prologues
                 ops.ln_qkv_rope_linear(hidden, None, None, eps, qkv_w, qkv_s, qkv, positions, self.cos_sin_cache,
-                                       kc, vc, md.slot_mapping, nh, nkv, hd)                       # :373-374,183-226
+                                       kc, vc, md.slot_mapping, nh, nkv, hd, **kvs)                # :373-374,183-226
                 if hq:
                     # merge + head Hadamard spread over 8 workgroups per token (fp16 + partial row maxima), the Quantizer
                     # of :235-238 in the o_proj launch's prologue: same bits as the two calls of the else branch
                     ops.paged_attention(qkv, row, kc, vc, md.block_tables, md.ctx_lens, md.q_start, T, md.max_q_len, nh,
-                                        self.sm_scale, md.n_splits, s.attn_ws, None)
+                                        self.sm_scale, md.n_splits, s.attn_ws, None, **kvs)
                     if self.head_had_K == 1:
                         ops.heads_hadamard_merged_spread(s.attn_ws, md.ctx_lens.numel() * md.max_q_len, md.n_splits, T, nh, hd,
                                                          self.head_had_scale, had16, s.had_part_amax[:T])
@@ -346,7 +363,7 @@ class QuarotLlamaForCausalLM:
                     ops.rowwise_scaled_linear_s4s4_residual_hq(had16, s.had_part_amax[:T], 1.0, layer.o_proj.weight,
                                                                layer.o_proj._scales(), hidden, hidden)
                 else:
-                    self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, q1, sc, None)        # :213-238
+                    self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, q1, sc, None, kvs=kvs)        # :213-238
                     ops.rowwise_scaled_linear_s4s4_residual(q1, sc, layer.o_proj.weight, layer.o_proj._scales(), hidden, hidden)
                 ops.ln_gate_up_silu_linear(hidden, None, None, eps, gu_w, gu_s, act)                # :380-388,266-284
                 ops.mlp_hadamard(act, self.had_rem_dim, self.had_K, self.mlp_had_scale, q=q3, scale=sc)
@@ -368,34 +385,35 @@ class QuarotLlamaForCausalLM:
                 self._add_norm_fp16(normed, hidden, delta, eps)
                 x, xs = normed, None
             if xp32:
-                ops.qkv_rope_linear_xp32(x, qkv_w, qkv_s, qkv, positions, self.cos_sin_cache, kc, vc, md.slot_mapping, nh, nkv, hd, T)
+                ops.qkv_rope_linear_xp32(x, qkv_w, qkv_s, qkv, positions, self.cos_sin_cache, kc, vc, md.slot_mapping, nh, nkv, hd, T,
+                                         **kvs)
             elif fuse:
                 ops.qkv_rope_linear(x, xs, qkv_w, qkv_s, qkv, positions, self.cos_sin_cache, kc, vc, md.slot_mapping,
-                                    nh, nkv, hd, xp=xp, tokens=T)
+                                    nh, nkv, hd, xp=xp, tokens=T, **kvs)
             else:
                 if w4a4:
                     ops.rowwise_scaled_linear_cutlass_s4s4_unified(q1, sc, qkv_w, qkv_s, None, qkv)
                 else:
                     self._w4a16(normed, layer.qkv_proj, qkv)
-                ops.rope_kv_write(positions, qkv, self.cos_sin_cache, kc, vc, md.slot_mapping, nh, nkv, hd)
+                ops.rope_kv_write(positions, qkv, self.cos_sin_cache, kc, vc, md.slot_mapping, nh, nkv, hd, **kvs)
             # attention -> heads hadamard (+ quant) -> o_proj -> residual + post_attention_layernorm     :231-243,380-387
             if w4a4:
-                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, q1, sc, None)
+                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, q1, sc, None, kvs=kvs)
                 ops.rowwise_scaled_linear_cutlass_s4s4_unified(q1, sc, layer.o_proj.weight, layer.o_proj._scales(), None, o)
                 ops.add_rms_norm_i4(q1, sc, hidden, hidden, o, eps)
                 x, xs = q1, sc
             elif xp:
-                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, None, None, had_x, xp=True)
+                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, None, None, had_x, xp=True, kvs=kvs)
                 self._w4a16(had_x, layer.o_proj, o, xp=True, tokens=T)
                 ops.add_rms_norm_fp16(normed_x, hidden, hidden, o, eps, xp=True)
                 x, xs = normed_x, None
             elif xp32:
-                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, None, None, had_x, xp=True)
+                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, None, None, had_x, xp=True, kvs=kvs)
                 ops.w4a16_linear_xp32(had_x, layer.o_proj.weight, layer.o_proj._scales(), o, T)
                 ops.add_rms_norm_fp16(normed_x, hidden, hidden, o, eps, xp=True)
                 x, xs = normed_x, None
             else:
-                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, None, None, had)
+                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, None, None, had, kvs=kvs)
                 if tp_on:   # row-parallel o_proj over this rank's K range of the shared buffer: raw fp32 sums,
                     # all-reduce in fp32, then scale + ONE fp16 rounding + residual add inside the norm (as on one GPU)
                     k0, k1 = self.tp.k_range(cfg.hidden_size)
@@ -538,7 +556,7 @@ class QuarotLlamaForCausalLM:
 
     # ------------------------------------------------------------------ module-wise path (reference op order)
     def forward_modulewise(self, input_ids, positions, kv_caches, attn_metadata: AttentionMetadata, w4a4=False,
-                           attn_override=None):
+                           attn_override=None, kv_scales=None):
         """attn_override (tests): per layer an fp16 [T, q_size] tensor that REPLACES the attention output of that layer
         (teacher forcing of the one stage whose fp32 summation order the hardware fixes)."""
         cfg, md = self.config, attn_metadata
@@ -554,16 +572,17 @@ class QuarotLlamaForCausalLM:
                                                              cfg.head_dim, md.n_splits), dtype=torch.uint8, device=self.device)
         for li, layer in enumerate(self.layers):
             kc, vc = kv_caches[li]
+            kvs = self._kv_kw(li, kc, kv_scales)
             residual = hidden
             x = self.norm(hidden, **kw)
             qkv = layer.qkv_proj(x, **kw)
             q, k, v = qkv.split([cfg.q_size, cfg.kv_size, cfg.kv_size], dim=-1)
             ops.rotary_embedding(positions, q, k, cfg.head_dim, self.cos_sin_cache)
             ops.reshape_and_cache_flash(k.view(T, cfg.num_key_value_heads, cfg.head_dim),
-                                        v.view(T, cfg.num_key_value_heads, cfg.head_dim), kc, vc, md.slot_mapping)
+                                        v.view(T, cfg.num_key_value_heads, cfg.head_dim), kc, vc, md.slot_mapping, **kvs)
             attn = torch.empty(T, cfg.q_size, dtype=torch.float16, device=self.device)
             ops.paged_attention(qkv, qkv.shape[1], kc, vc, md.block_tables, md.ctx_lens, md.q_start, T, md.max_q_len,
-                                cfg.num_attention_heads, self.sm_scale, md.n_splits, ws, attn)
+                                cfg.num_attention_heads, self.sm_scale, md.n_splits, ws, attn, **kvs)
             if attn_override is not None:
                 attn.copy_(attn_override[li])
             a = attn.view(-1, cfg.num_attention_heads, cfg.head_dim)

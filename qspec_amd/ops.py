@@ -45,6 +45,25 @@ def _opt(t: Optional[torch.Tensor], name: str, dtype=None):
     return None if t is None else _chk(t, name, dtype)
 
 
+_KV8 = (torch.uint8, torch.float8_e4m3fn)
+
+
+def _kv(key_cache, value_cache, k_scale: float = 1.0, v_scale: float = 1.0):
+    """Cache arguments of an entry that takes (key_cache, value_cache): the name suffix and the argument tuple.
+    fp16 caches -> the base entry; uint8 / float8_e4m3fn caches (kv_cache_dtype = "fp8") -> its `_kv8` form, which takes the
+    per-tensor scales behind the two pointers.  A scale other than 1 with an fp16 cache is an error, not ignored."""
+    if key_cache.dtype != value_cache.dtype:
+        raise RuntimeError(f"key_cache is {key_cache.dtype}, value_cache {value_cache.dtype}")
+    if key_cache.dtype in _KV8:
+        k_scale, v_scale = float(k_scale), float(v_scale)
+        if not (0.0 < k_scale < float("inf") and 0.0 < v_scale < float("inf")):
+            raise ValueError(f"k_scale={k_scale}, v_scale={v_scale} must be positive and finite")
+        return "_kv8", (_chk(key_cache, "key_cache", _KV8), _chk(value_cache, "value_cache", _KV8), k_scale, v_scale)
+    if float(k_scale) != 1.0 or float(v_scale) != 1.0:
+        raise ValueError("k_scale / v_scale belong to an fp8 KV cache; the cache tensors are fp16")
+    return "", (_chk(key_cache, "key_cache", _F16), _chk(value_cache, "value_cache", _F16))
+
+
 def _call(name: str, *args):
     lib = _lib.load()
     _lib.check(getattr(lib, name)(*args), lib)
@@ -124,11 +143,12 @@ def w4a16_linear_partial_xp32(x, wq, part, slices: int, tokens: int):
 
 
 def qkv_rope_linear_xp32(x, wq, w_scale, qkv, positions, cos_sin_cache, key_cache, value_cache, slot_mapping, num_heads,
-                         num_kv_heads, head_size, tokens: int):
+                         num_kv_heads, head_size, tokens: int, k_scale: float = 1.0, v_scale: float = 1.0):
     N, K = wq.shape[0], wq.shape[1] * 2
-    _call("qspec_qkv_rope_linear_w4a16_xp32", _xp32_tiles(x, "x", K), _chk(wq, "wq", (_I8, _U8)), _chk(w_scale, "w_scale", _F16),
+    kv8, caches = _kv(key_cache, value_cache, k_scale, v_scale)
+    _call("qspec_qkv_rope_linear_w4a16_xp32" + kv8, _xp32_tiles(x, "x", K), _chk(wq, "wq", (_I8, _U8)), _chk(w_scale, "w_scale", _F16),
           _chk(qkv, "qkv", _F16), tokens, N, K, _chk(positions, "positions", _I64), _chk(cos_sin_cache, "cos_sin_cache", _F16),
-          _chk(key_cache, "key_cache", _F16), _chk(value_cache, "value_cache", _F16), _chk(slot_mapping, "slot_mapping", _I64),
+          *caches, _chk(slot_mapping, "slot_mapping", _I64),
           num_heads, num_kv_heads, head_size, cos_sin_cache.shape[-1], _stream())
     return qkv
 
@@ -270,7 +290,8 @@ def qkv_rope_linear_supported(w4a4: bool, M: int, N: int, K: int, head_size: int
 
 
 def qkv_rope_linear(x, x_scale, wq, w_scale, qkv, positions, cos_sin_cache, key_cache, value_cache, slot_mapping,
-                    num_heads, num_kv_heads, head_size, xp: bool = False, tokens=None):
+                    num_heads, num_kv_heads, head_size, xp: bool = False, tokens=None, k_scale: float = 1.0,
+                    v_scale: float = 1.0):
     """qkv GEMM + rotary_embedding + reshape_and_cache_flash in one launch (quarot_llama.py:183-226).
     x_scale is None -> W4A16 (x fp16 [M,K]); else W4A4 (x packed int4 [M,K/2])."""
     N = wq.shape[0]
@@ -278,15 +299,15 @@ def qkv_rope_linear(x, x_scale, wq, w_scale, qkv, positions, cos_sin_cache, key_
     M = x.shape[0] if tokens is None else tokens    # xp: x is the 16-row tile, tokens the rows in use
     if xp:
         _xp_tile(x, "x", K)
-    common = (_chk(positions, "positions", _I64), _chk(cos_sin_cache, "cos_sin_cache", _F16),
-              _chk(key_cache, "key_cache", _F16), _chk(value_cache, "value_cache", _F16),
+    kv8, caches = _kv(key_cache, value_cache, k_scale, v_scale)
+    common = (_chk(positions, "positions", _I64), _chk(cos_sin_cache, "cos_sin_cache", _F16), *caches,
               _chk(slot_mapping, "slot_mapping", _I64), num_heads, num_kv_heads, head_size, cos_sin_cache.shape[-1])
     if x_scale is not None:
-        _call("qspec_qkv_rope_linear_s4s4", _chk(x, "xq", (_I8, _U8)), _chk(x_scale, "x_scale", _F16),
+        _call("qspec_qkv_rope_linear_s4s4" + kv8, _chk(x, "xq", (_I8, _U8)), _chk(x_scale, "x_scale", _F16),
               _chk(wq, "wq", (_I8, _U8)), _chk(w_scale, "w_scale", _F16), _chk(qkv, "qkv", _F16), M, N, K, *common,
               _stream())
     else:
-        _call("qspec_qkv_rope_linear_w4a16" + ("_xp" if xp else ""), _chk(x, "x", _F16), _chk(wq, "wq", (_I8, _U8)),
+        _call("qspec_qkv_rope_linear_w4a16" + ("_xp" if xp else "") + kv8, _chk(x, "x", _F16), _chk(wq, "wq", (_I8, _U8)),
               _chk(w_scale, "w_scale", _F16), _chk(qkv, "qkv", _F16), M, N, K, *common,
               w4a16_workspace(x.device).data_ptr(), _stream())
     return qkv
@@ -352,15 +373,17 @@ def ln_linear_error_word(device):
 
 
 def ln_qkv_rope_linear(hidden_in, delta, hidden_out, eps, wq, w_scale, qkv, positions, cos_sin_cache, key_cache,
-                       value_cache, slot_mapping, num_heads, num_kv_heads, head_size):
+                       value_cache, slot_mapping, num_heads, num_kv_heads, head_size, k_scale: float = 1.0,
+                       v_scale: float = 1.0):
     """Draft pass: hidden_out = hidden_in + delta; LN + int4 quant; qkv GEMM; RoPE; KV write -- one launch
     (quarot_llama.py:373-374 + 183-226)."""
     M, K = hidden_in.shape
     N = wq.shape[0]
-    _call("qspec_ln_qkv_rope_linear_s4s4", _chk(hidden_in, "hidden_in", _F16), _opt(delta, "delta", _F16),
+    kv8, caches = _kv(key_cache, value_cache, k_scale, v_scale)
+    _call("qspec_ln_qkv_rope_linear_s4s4" + kv8, _chk(hidden_in, "hidden_in", _F16), _opt(delta, "delta", _F16),
           _opt(hidden_out, "hidden_out", _F16), float(eps), _chk(wq, "wq", (_I8, _U8)), _chk(w_scale, "w_scale", _F16),
           _chk(qkv, "qkv", _F16), M, N, K, _chk(positions, "positions", _I64), _chk(cos_sin_cache, "cos_sin_cache", _F16),
-          _chk(key_cache, "key_cache", _F16), _chk(value_cache, "value_cache", _F16),
+          *caches,
           _chk(slot_mapping, "slot_mapping", _I64), num_heads, num_kv_heads, head_size, cos_sin_cache.shape[-1],
           _opt(ln_linear_workspace(hidden_in.device, M), "sync_workspace"), _stream())
     return qkv
@@ -561,20 +584,20 @@ def rotary_embedding(positions, query, key, head_size: int, cos_sin_cache, is_ne
           query.stride(0), key.stride(0), _stream())
 
 
-def reshape_and_cache_flash(key, value, key_cache, value_cache, slot_mapping):
+def reshape_and_cache_flash(key, value, key_cache, value_cache, slot_mapping, k_scale: float = 1.0, v_scale: float = 1.0):
     """torch.ops._C_cache_ops.reshape_and_cache_flash (csrc/cache_kernels.cu:304); key/value [T, n_kv, d]."""
     T, nkv, d = key.shape
-    _call("qspec_reshape_and_cache_flash", key.data_ptr(), value.data_ptr(), _chk(key_cache, "key_cache", _F16),
-          _chk(value_cache, "value_cache", _F16), _chk(slot_mapping, "slot_mapping", _I64), T, nkv, d, key.stride(0),
+    kv8, caches = _kv(key_cache, value_cache, k_scale, v_scale)
+    _call("qspec_reshape_and_cache_flash" + kv8, key.data_ptr(), value.data_ptr(), *caches, _chk(slot_mapping, "slot_mapping", _I64), T, nkv, d, key.stride(0),
           value.stride(0), _stream())
 
 
 def rope_kv_write(positions, qkv, cos_sin_cache, key_cache, value_cache, slot_mapping, num_heads, num_kv_heads,
-                  head_size):
+                  head_size, k_scale: float = 1.0, v_scale: float = 1.0):
     T = qkv.shape[0]
-    _call("qspec_rope_kv_write", _chk(positions, "positions", _I64), _chk(qkv, "qkv", _F16),
-          _chk(cos_sin_cache, "cos_sin_cache", _F16), _chk(key_cache, "key_cache", _F16),
-          _chk(value_cache, "value_cache", _F16), _chk(slot_mapping, "slot_mapping", _I64), T, num_heads,
+    kv8, caches = _kv(key_cache, value_cache, k_scale, v_scale)
+    _call("qspec_rope_kv_write" + kv8, _chk(positions, "positions", _I64), _chk(qkv, "qkv", _F16),
+          _chk(cos_sin_cache, "cos_sin_cache", _F16), *caches, _chk(slot_mapping, "slot_mapping", _I64), T, num_heads,
           num_kv_heads, head_size, cos_sin_cache.shape[-1], _stream())
 
 
@@ -583,12 +606,13 @@ def paged_attention_workspace_bytes(max_tokens, num_heads, head_size, n_splits) 
 
 
 def paged_attention(q, q_stride, key_cache, value_cache, block_tables, ctx_lens, q_start, tokens, max_q_len,
-                    num_heads, sm_scale, n_splits, workspace, out):
-    """flash_attn_with_kvcache / flash_attn_varlen_func over the paged cache (flash_attn.py:741-830)."""
+                    num_heads, sm_scale, n_splits, workspace, out, k_scale: float = 1.0, v_scale: float = 1.0):
+    """flash_attn_with_kvcache / flash_attn_varlen_func over the paged cache (flash_attn.py:741-830); an fp8 cache
+    (uint8 / float8_e4m3fn tensors) is read as float(e4m3) * scale (paged_attn.py, kv_cache_dtype = "fp8")."""
     nb, bs, nkv, d = key_cache.shape
     n_seqs = ctx_lens.numel()
-    _call("qspec_paged_attention", q.data_ptr(), q_stride, _chk(key_cache, "key_cache", _F16),
-          _chk(value_cache, "value_cache", _F16), _chk(block_tables, "block_tables", _I32), block_tables.shape[1],
+    kv8, caches = _kv(key_cache, value_cache, k_scale, v_scale)
+    _call("qspec_paged_attention" + kv8, q.data_ptr(), q_stride, *caches, _chk(block_tables, "block_tables", _I32), block_tables.shape[1],
           _chk(ctx_lens, "ctx_lens", _I32), _chk(q_start, "q_start", _I32), n_seqs, tokens, max_q_len, num_heads, nkv,
           d, bs, float(sm_scale), n_splits, workspace.data_ptr(), _opt(out, "out", _F16), _stream())
 

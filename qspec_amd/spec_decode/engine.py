@@ -61,7 +61,19 @@ def n_splits_for(ctx: int, n_groups: int = 0) -> int:
 class QSpecEngine:
     def __init__(self, model: QuarotLlamaForCausalLM, num_speculative_tokens: int = 3, max_batch: int = 4,
                  max_model_len: int = 1024, block_size: int = 16, max_new_tokens: int = 1024, use_graph: bool = True,
-                 seed: int = 0, num_blocks: Optional[int] = None, acceptance_sampler=None):
+                 seed: int = 0, num_blocks: Optional[int] = None, acceptance_sampler=None, kv_cache_dtype: str = "auto",
+                 kv_scales=None):
+        """kv_cache_dtype: "auto" (fp16 cache) or "fp8" / "fp8_e4m3" (one e4m3 byte per element, half the cache bytes;
+        include/qspec_hip.h, "FP8 KV cache").  kv_scales: per layer (k_scale, v_scale) for the fp8 cache, kept on THIS engine
+        and handed to every forward (the model, which other engines may share, is not touched); None keeps the model's
+        (read from the checkpoint) or 1.0."""
+        if kv_cache_dtype not in ("auto", "fp8", "fp8_e4m3"):
+            raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}: 'auto', 'fp8' or 'fp8_e4m3'")
+        self.kv_cache_dtype = "auto" if kv_cache_dtype == "auto" else "fp8"
+        if kv_scales is not None and self.kv_cache_dtype != "fp8":
+            raise ValueError("kv_scales belong to kv_cache_dtype='fp8'")
+        if self.kv_cache_dtype == "fp8" and getattr(model, "tp", None) is not None and getattr(model.tp, "world", 1) > 1:
+            raise NotImplementedError("fp8 KV cache with tensor parallelism")
         self.model = model
         self.cfg = cfg = model.config
         if max_model_len > cfg.max_position_embeddings:
@@ -83,8 +95,15 @@ class QSpecEngine:
         if self.num_blocks < 1:
             raise ValueError("the KV cache needs at least one block")
         shape = (self.num_blocks, block_size, cfg.num_key_value_heads, cfg.head_dim)
-        self.kv_caches = [(torch.zeros(shape, dtype=torch.float16, device=dev),
-                           torch.zeros(shape, dtype=torch.float16, device=dev)) for _ in range(cfg.num_hidden_layers)]
+        kv_dtype = torch.uint8 if self.kv_cache_dtype == "fp8" else torch.float16   # byte 0 = e4m3 +0.0
+        if kv_scales is not None:
+            kv_scales = [(float(a), float(b)) for a, b in kv_scales]
+            if len(kv_scales) != cfg.num_hidden_layers or any(not (a > 0 and b > 0) for a, b in kv_scales):
+                raise ValueError("kv_scales: one positive (k_scale, v_scale) pair per layer")
+        self.kv_scales = kv_scales
+        self._kv_fw = {} if kv_scales is None else {"kv_scales": kv_scales}   # forward() keywords; empty unless fp8 + own scales
+        self.kv_caches = [(torch.zeros(shape, dtype=kv_dtype, device=dev),
+                           torch.zeros(shape, dtype=kv_dtype, device=dev)) for _ in range(cfg.num_hidden_layers)]
         if self.num_blocks >= B * self.blocks_per_seq:
             self.block_tables = torch.arange(B * self.blocks_per_seq, dtype=i32, device=dev).view(B, self.blocks_per_seq).contiguous()
             self._capacity = [self.blocks_per_seq * block_size] * B    # tokens the slot's block table covers (host)
@@ -289,7 +308,7 @@ class QSpecEngine:
         q_start = torch.tensor([0] + list(torch.tensor(lens).cumsum(0).tolist()), dtype=torch.int32, device=dev)
         md = AttentionMetadata(slot_map, self.block_tables[list(slots)].contiguous(),
                                torch.tensor(lens, dtype=torch.int32, device=dev), q_start, Tmax, 1)
-        hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False)
+        hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False, **self._kv_fw)
         last = (q_start[1:].long() - 1)
         logits = self.model.compute_logits(hs[last].contiguous(), s)
         probs = torch.empty(n, cfg.vocab_size, dtype=torch.float32, device=dev)
@@ -335,7 +354,7 @@ class QSpecEngine:
         md = AttentionMetadata(slots, self.block_tables[b:b + 1].contiguous(),
                                torch.tensor([T], dtype=torch.int32, device=dev),
                                torch.tensor([0, T], dtype=torch.int32, device=dev), T, n_splits_for(T))
-        hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False)
+        hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False, **self._kv_fw)
         logits = self.model.compute_logits(hs[T - 1:T], s)
         probs = torch.empty(1, cfg.vocab_size, dtype=torch.float32, device=dev)
         tok = torch.empty(1, dtype=torch.int64, device=dev)
@@ -708,7 +727,7 @@ class QSpecEngine:
         draft_sv = tp is not None and getattr(tp, "shard_draft_vocab", False)   # vocab-parallel lm_head on the draft pass too
         for i in range(k):
             hs = m.forward(self.d_tokens, self.d_pos, self.kv_caches, self.md_draft, self.scratch_draft, w4a4=True,
-                           embedded=emb_d is not None)
+                           embedded=emb_d is not None, **self._kv_fw)
             if self._mode_sampling:   # draft tokens are SAMPLED from the processed draft distribution (sampler.py:216-316)
                 extra = {}
                 if self._mode_processing:   # draft step i proposes d_{i+1}: it sees d_1 .. d_i in flight
@@ -732,7 +751,7 @@ class QSpecEngine:
         ops.spec_prepare_verify(self.last_token, draft_ids, self.eff_lens, self.block_tables, bs, self.v_tokens,
                                 self.v_pos, self.v_slots, self.v_ctx, embed=emb_v)
         hs = m.forward(self.v_tokens, self.v_pos, self.kv_caches, self.md_verify, self.scratch_verify, w4a4=False,
-                       embedded=emb_v is not None)
+                       embedded=emb_v is not None, **self._kv_fw)
         hook = self._verify_logits_hook(draft_ids)
         seeded = {}
         if self._mode_sampling:
@@ -786,7 +805,7 @@ class QSpecEngine:
         torch.mul(self.seq_lens, self.step_mask, out=self.eff_lens)
         ops.spec_prepare_draft(self.last_token, self.eff_lens, self.block_tables, bs, self.d_tokens, self.d_pos,
                                self.d_slots, self.d_ctx)                   # [last token] at position seq_len - 1
-        hs = m.forward(self.d_tokens, self.d_pos, self.kv_caches, self.md_draft, self.scratch_draft, w4a4=False)
+        hs = m.forward(self.d_tokens, self.d_pos, self.kv_caches, self.md_draft, self.scratch_draft, w4a4=False, **self._kv_fw)
         logits = m.compute_logits(hs, self.scratch_draft)
         processing = self._processing_on()
         if processing:   # position j = 0, nothing in flight: catch up with the committed tokens, then the pre-pass

@@ -6,7 +6,7 @@
 vllm/spec_decode/spec_decode_worker.py:53-113,118-470,461-560,582-664,722-755,972-1110,1178-1210.
 
 The factory binds the way the reference's does: `kwargs["vllm_config"]` (duck-typed: `model_config.{hf_config,
-max_model_len, model, seed, max_logprobs}`, `cache_config.{block_size, gpu_memory_utilization, swap_space_bytes}`,
+max_model_len, model, seed, max_logprobs}`, `cache_config.{block_size, gpu_memory_utilization, swap_space_bytes, cache_dtype}`,
 `scheduler_config.{max_num_seqs, max_num_batched_tokens}`, `speculative_config.{num_speculative_tokens,
 speculative_disable_by_batch_size, disable_log_stats, disable_logprobs, draft_token_acceptance_method}`,
 `parallel_config.{tensor_parallel_size, pipeline_parallel_size}`, `load_config.load_format`) plus `local_rank`, `rank`,
@@ -263,6 +263,7 @@ def create_spec_worker(*args, **kwargs) -> "SpecDecodeWorker":
             is_driver_worker=kwargs.get("is_driver_worker", kwargs.get("rank", 0) == 0),
             gpu_memory_utilization=getattr(cc, "gpu_memory_utilization", 0.9),
             swap_space_bytes=getattr(cc, "swap_space_bytes", 0),
+            cache_dtype=getattr(cc, "cache_dtype", "auto"),
             max_num_batched_tokens=getattr(sc, "max_num_batched_tokens", None),
             max_logprobs=getattr(mc, "max_logprobs", 20),
             disable_logprobs=getattr(spec, "disable_logprobs", True))
@@ -286,7 +287,7 @@ def create_spec_worker(*args, **kwargs) -> "SpecDecodeWorker":
                             max_num_batched_tokens=kwargs.get("max_num_batched_tokens"),
                             max_logprobs=kwargs.get("max_logprobs", 20),
                             disable_logprobs=getattr(spec, "disable_logprobs", True),
-                            memory_probe=kwargs.get("memory_probe"))
+                            memory_probe=kwargs.get("memory_probe"), cache_dtype=kwargs.get("cache_dtype", "auto"))
 
 
 class SpecDecodeWorker:
@@ -297,7 +298,14 @@ class SpecDecodeWorker:
                  distributed_init_method: Optional[str] = None, is_driver_worker: bool = True,
                  gpu_memory_utilization: float = 0.9, swap_space_bytes: int = 0,
                  max_num_batched_tokens: Optional[int] = None, max_logprobs: int = 20, disable_logprobs: bool = True,
-                 memory_probe: Optional[Callable[[], Tuple[int, int, int]]] = None):
+                 memory_probe: Optional[Callable[[], Tuple[int, int, int]]] = None, cache_dtype: str = "auto"):
+        # cache_config.cache_dtype (vllm/config.py CacheConfig): "auto" = the model's fp16; "fp8" / "fp8_e4m3" = OCP e4m3
+        # bytes (include/qspec_hip.h, "FP8 KV cache").  Anything else is refused here, not served from an fp16 cache.
+        if cache_dtype not in ("auto", "fp8", "fp8_e4m3"):
+            raise ValueError(f"cache_config.cache_dtype = {cache_dtype!r}: this worker serves 'auto', 'fp8' and 'fp8_e4m3'")
+        self.kv_cache_dtype = "auto" if cache_dtype == "auto" else "fp8"
+        if self.kv_cache_dtype == "fp8" and tensor_parallel_size > 1:
+            raise NotImplementedError("fp8 KV cache with tensor parallelism")
         self.model_config = model_config
         self.speculative_config = speculative_config
         self.max_num_seqs = max_num_seqs
@@ -385,10 +393,12 @@ class SpecDecodeWorker:
         return self._model
 
     def cache_block_size_bytes(self) -> int:
-        """vllm/worker/cache_engine.py:101-119: K and V of one block over all layers, fp16.  The KV cache is NOT
-        sharded under this worker's tensor parallelism (replicated draft pass), so kv heads are not divided."""
+        """vllm/worker/cache_engine.py:101-119: K and V of one block over all layers, 2 bytes per element (fp16) or 1
+        (cache_dtype fp8).  The KV cache is NOT sharded under this worker's tensor parallelism (replicated draft pass), so
+        kv heads are not divided."""
         c = self.model_config
-        return 2 * c.num_hidden_layers * self.block_size * c.num_key_value_heads * c.head_dim * 2
+        elem = 1 if self.kv_cache_dtype == "fp8" else 2
+        return 2 * c.num_hidden_layers * self.block_size * c.num_key_value_heads * c.head_dim * elem
 
     def _profile_memory(self) -> Tuple[int, int, int]:
         """(free bytes now, total bytes, peak increase of one profiled prompt pass + cycle).  vllm/worker/worker.py:176-205:
@@ -411,7 +421,7 @@ class SpecDecodeWorker:
         blocks_per_seq = (per_seq + k + 2 + self.block_size - 1) // self.block_size
         n_blocks = self.max_num_seqs * blocks_per_seq
         eng = self._engine_factory(self._model, k, self.max_num_seqs, self.max_model_len, self.block_size,
-                                   seed=self._seed, num_blocks=n_blocks, **self._sampler_kwargs())
+                                   seed=self._seed, num_blocks=n_blocks, **self._sampler_kwargs(), **self._kv_kwargs())
         kv_bytes = n_blocks * self.cache_block_size_bytes()
         tables = [list(range(b * blocks_per_seq, (b + 1) * blocks_per_seq)) for b in range(self.max_num_seqs)]
         eng.add_sequences_to(list(range(self.max_num_seqs)), [[0] * per_seq] * self.max_num_seqs, tables)
@@ -453,9 +463,14 @@ class SpecDecodeWorker:
                              "increasing `gpu_memory_utilization` or decreasing `max_model_len` when initializing the engine.")
         self.engine = self._engine_factory(self._model, self.speculative_config.num_speculative_tokens,
                                            self.max_num_seqs, self.max_model_len, self.block_size, seed=self._seed,
-                                           num_blocks=num_gpu_blocks, **self._sampler_kwargs())
+                                           num_blocks=num_gpu_blocks, **self._sampler_kwargs(), **self._kv_kwargs())
         self._metrics = AsyncMetricsCollector(self.engine.sampler)
         self._metrics.init_gpu_tensors(self._rank)
+
+    def _kv_kwargs(self) -> dict:
+        """Engine keywords of the fp8 KV cache; none for "auto", so an engine (or a test double) that predates them is
+        called exactly as before."""
+        return {"kv_cache_dtype": "fp8"} if self.kv_cache_dtype == "fp8" else {}
 
     def _sampler_kwargs(self) -> dict:
         """spec_decode_worker.py:95-110: the acceptance sampler named by `draft_token_acceptance_method`."""
