@@ -523,7 +523,7 @@ class QuarotLlamaForCausalLM:
 
     def sample_greedy(self, hidden_states, scratch: Scratch, probs, token, shard_vocab: bool = False, logits_hook=None):
         """compute_logits + Sampler.forward (greedy, modify_greedy_probs = False: sampler.py:216-316): probs [T, V] fp32,
-        token [T].  At decode-sized T on one GPU the lm_head launch and the softmax are fused (ops.lm_head_softmax_argmax);
+        token [T] (batches with non-greedy rows: QSpecEngine._sample).  At decode-sized T on one GPU the lm_head launch and the softmax are fused (ops.lm_head_softmax_argmax);
         a vocab-parallel lm_head, a large T or a logits hook (bench only) take the two-step path.  Same bits."""
         T = hidden_states.shape[0]
         V, K = self.lm_head.shape
@@ -535,24 +535,6 @@ class QuarotLlamaForCausalLM:
         if logits_hook is not None:
             logits_hook(logits)
         ops.softmax_argmax(logits, probs, token)
-
-    def sample(self, hidden_states, scratch: Scratch, probs, token, temperature, top_k, top_p, rng_state,
-               shard_vocab: bool = False, logits_hook=None, exponential=None, workspace=None, process=None, min_p=None,
-               **seeded):
-        """compute_logits + Sampler.forward for batches with non-greedy rows (sampler.py:216-316): temperature, top-k / top-p,
-        softmax, multinomial by exponential noise; rows whose temperature is 0 take the argmax.  probs [T, V] fp32 (the
-        PROCESSED distribution: what the rejection sampler must see), token [T].  workspace: the sampler's (zeroed) histogram
-        workspace; seeded: the per-sequence seed arguments of ops.sample_top_k_top_p (seq_seeds, seq_seeded, base_pos,
-        rows_per_seq, j_base, draw_stream).  process: a callable(raw logits) -> processed logits run between the logits
-        (+ the bench-only hook) and the sampler -- the engine's min_tokens / penalty pre-pass (ops.process_logits, out of place:
-        the raw logits stay in scratch.logits); min_p [T] fp32: _apply_min_p inside the sampler."""
-        logits = self.compute_logits(hidden_states, scratch, shard_vocab=shard_vocab)
-        if logits_hook is not None:
-            logits_hook(logits)
-        if process is not None:
-            logits = process(logits)
-        ops.sample_top_k_top_p(logits, probs, token, temperature, top_k, top_p, exponential=exponential, rng_state=rng_state,
-                               workspace=workspace, min_p=min_p, **seeded)
 
     # ------------------------------------------------------------------ module-wise path (reference op order)
     def forward_modulewise(self, input_ids, positions, kv_caches, attn_metadata: AttentionMetadata, w4a4=False,

@@ -821,12 +821,9 @@ def logit_table_catch_up(tok_table, counted_len, need_counts, gen_tokens, gen_le
           _chk(gen_lens, "gen_lens", _I32), _stream())
 
 
-def process_logits(logits, out, tok_table, repetition, frequency, presence, min_tokens, gen_base, gen_lens, stop_ids,
-                   num_stop_ids, draft_ids=None, rows_per_seq: int = 1, j_base: int = 0, slot_ids=None, active_lens=None):
-    """_apply_min_tokens_penalty + apply_penalties per row (sampler.py:258-266), out of place: out [T, V] fp16.  Row t belongs to
-    sequence t // rows_per_seq (slot slot_ids[sequence] or the sequence index) with j = j_base + t % rows_per_seq and sees the
-    in-flight tokens draft_ids[0 .. j, slot] (draft_ids [n, num_slots] int64, step-major as the engine keeps them; any strides).
-    The per-slot arrays are device tensors read when the call runs."""
+def _process_logits_args(logits, out, tok_table, repetition, frequency, presence, min_tokens, gen_base, gen_lens, stop_ids,
+                         num_stop_ids, draft_ids, rows_per_seq: int, j_base: int, slot_ids, active_lens):
+    """The checks and the leading C arguments process_logits and process_logits_constrained share."""
     T, V = logits.shape
     B = tok_table.shape[0]
     if tok_table.shape[1] != V or out.shape != logits.shape:
@@ -847,12 +844,22 @@ def process_logits(logits, out, tok_table, repetition, frequency, presence, min_
         if draft_ids.dim() != 2 or draft_ids.shape[1] < B or draft_ids.dtype != _I64 or not draft_ids.is_cuda:
             raise RuntimeError("draft_ids must be an int64 [steps, num_slots] GPU tensor")
         n_draft, di_sk, di_sb, di_ptr = draft_ids.shape[0], draft_ids.stride(0), draft_ids.stride(1), draft_ids.data_ptr()
-    _call("qspec_process_logits", _chk(logits, "logits", _F16), _chk(out, "out", _F16), T, V, _chk(tok_table, "tok_table", _I32),
-          B, _opt(slot_ids, "slot_ids", _I32), _opt(active_lens, "active_lens", _I32), _chk(repetition, "repetition", _F16),
-          _chk(frequency, "frequency", _F16), _chk(presence, "presence", _F16), _chk(min_tokens, "min_tokens", _I32),
-          _chk(gen_base, "gen_base", _I32), _chk(gen_lens, "gen_lens", _I32), _chk(stop_ids, "stop_ids", _I32),
-          _chk(num_stop_ids, "num_stop_ids", _I32), stop_ids.shape[1], di_ptr, n_draft, di_sb, di_sk, rows_per_seq, j_base,
-          _stream())
+    return (_chk(logits, "logits", _F16), _chk(out, "out", _F16), T, V, _chk(tok_table, "tok_table", _I32), B,
+            _opt(slot_ids, "slot_ids", _I32), _opt(active_lens, "active_lens", _I32), _chk(repetition, "repetition", _F16),
+            _chk(frequency, "frequency", _F16), _chk(presence, "presence", _F16), _chk(min_tokens, "min_tokens", _I32),
+            _chk(gen_base, "gen_base", _I32), _chk(gen_lens, "gen_lens", _I32), _chk(stop_ids, "stop_ids", _I32),
+            _chk(num_stop_ids, "num_stop_ids", _I32), stop_ids.shape[1], di_ptr, n_draft, di_sb, di_sk, rows_per_seq, j_base)
+
+
+def process_logits(logits, out, tok_table, repetition, frequency, presence, min_tokens, gen_base, gen_lens, stop_ids,
+                   num_stop_ids, draft_ids=None, rows_per_seq: int = 1, j_base: int = 0, slot_ids=None, active_lens=None):
+    """_apply_min_tokens_penalty + apply_penalties per row (sampler.py:258-266), out of place: out [T, V] fp16.  Row t belongs to
+    sequence t // rows_per_seq (slot slot_ids[sequence] or the sequence index) with j = j_base + t % rows_per_seq and sees the
+    in-flight tokens draft_ids[0 .. j, slot] (draft_ids [n, num_slots] int64, step-major as the engine keeps them; any strides).
+    The per-slot arrays are device tensors read when the call runs."""
+    _call("qspec_process_logits", *_process_logits_args(logits, out, tok_table, repetition, frequency, presence, min_tokens,
+                                                        gen_base, gen_lens, stop_ids, num_stop_ids, draft_ids, rows_per_seq,
+                                                        j_base, slot_ids, active_lens), _stream())
     return out
 
 
@@ -929,16 +936,9 @@ def process_logits_constrained(logits, out, tok_table, repetition, frequency, pr
     allowed_token_ids, single-token bad words) and the multi-token bad words matched against the request's outputs -- the tail
     it had before admission, gen_tokens[slot][:gen_lens], the in-flight draft_ids[0 .. j, slot].  The arrays are those of a
     TokenConstraints; a slot whose meta row is zero gets the bits of process_logits."""
-    T, V = logits.shape
-    B = tok_table.shape[0]
-    if tok_table.shape[1] != V or out.shape != logits.shape:
-        raise RuntimeError("tok_table / out do not match the logits")
-    for t, name in ((repetition, "repetition"), (frequency, "frequency"), (presence, "presence"), (min_tokens, "min_tokens"),
-                    (gen_base, "gen_base"), (gen_lens, "gen_lens"), (num_stop_ids, "num_stop_ids")):
-        if t.numel() < B:
-            raise RuntimeError(f"{name} has {t.numel()} entries, the table has {B} slots")
-    if stop_ids.dim() != 2 or stop_ids.shape[0] < B:
-        raise RuntimeError("stop_ids must be [num_slots, width]")
+    V, B = logits.shape[1], tok_table.shape[0]
+    args = _process_logits_args(logits, out, tok_table, repetition, frequency, presence, min_tokens, gen_base, gen_lens, stop_ids,
+                                num_stop_ids, draft_ids, rows_per_seq, j_base, slot_ids, active_lens)
     if deny.dim() != 2 or deny.shape[0] < B or deny.shape[1] * 32 < V:
         raise RuntimeError("deny must be [num_slots, >= ceil(vocab / 32)]")
     for t, shape, name in ((meta, (4,), "meta"), (bias_ids, (MAX_LOGIT_BIAS,), "bias_ids"), (bias_vals, (MAX_LOGIT_BIAS,), "bias_vals"),
@@ -948,22 +948,7 @@ def process_logits_constrained(logits, out, tok_table, repetition, frequency, pr
             raise RuntimeError(f"{name} must be [num_slots, {', '.join(str(d) for d in shape)}]")
     if gen_tokens.dim() != 2 or gen_tokens.shape[0] < B:
         raise RuntimeError("gen_tokens must be [num_slots, capacity]")
-    nseq = (T + rows_per_seq - 1) // max(1, rows_per_seq)
-    if slot_ids is not None and slot_ids.numel() < nseq:
-        raise RuntimeError(f"slot_ids has {slot_ids.numel()} entries, {nseq} sequences need one each")
-    if active_lens is not None and active_lens.numel() < B:
-        raise RuntimeError("active_lens is shorter than the table")
-    n_draft, di_sb, di_sk, di_ptr = 0, 0, 0, None
-    if draft_ids is not None:
-        if draft_ids.dim() != 2 or draft_ids.shape[1] < B or draft_ids.dtype != _I64 or not draft_ids.is_cuda:
-            raise RuntimeError("draft_ids must be an int64 [steps, num_slots] GPU tensor")
-        n_draft, di_sk, di_sb, di_ptr = draft_ids.shape[0], draft_ids.stride(0), draft_ids.stride(1), draft_ids.data_ptr()
-    _call("qspec_process_logits_constrained", _chk(logits, "logits", _F16), _chk(out, "out", _F16), T, V,
-          _chk(tok_table, "tok_table", _I32), B, _opt(slot_ids, "slot_ids", _I32), _opt(active_lens, "active_lens", _I32),
-          _chk(repetition, "repetition", _F16), _chk(frequency, "frequency", _F16), _chk(presence, "presence", _F16),
-          _chk(min_tokens, "min_tokens", _I32), _chk(gen_base, "gen_base", _I32), _chk(gen_lens, "gen_lens", _I32),
-          _chk(stop_ids, "stop_ids", _I32), _chk(num_stop_ids, "num_stop_ids", _I32), stop_ids.shape[1], di_ptr, n_draft, di_sb,
-          di_sk, rows_per_seq, j_base, _chk(deny, "deny", _I32), deny.shape[1], _chk(meta, "meta", _I32),
+    _call("qspec_process_logits_constrained", *args, _chk(deny, "deny", _I32), deny.shape[1], _chk(meta, "meta", _I32),
           _chk(bias_ids, "bias_ids", _I32), _chk(bias_vals, "bias_vals", _F32), _chk(words, "words", _I32),
           _chk(word_lens, "word_lens", _I32), _chk(tail, "tail", _I32), _chk(gen_tokens, "gen_tokens", _I64),
           gen_tokens.shape[1], _stream())

@@ -35,6 +35,7 @@ from .. import ops
 from ..model import AttentionMetadata, QuarotLlamaForCausalLM, Scratch
 from .metrics import SpecDecodeWorkerMetrics, metrics_from_counters
 from .rejection_sampler import RejectionSampler
+from .slot_sampling import SlotSampling
 
 ATTN_CHUNK = 128  # keys per context split of the attention kernel (QS_ATT_CHUNK)
 
@@ -162,79 +163,30 @@ class QSpecEngine:
         self.scratch_verify = Scratch(cfg, T, B, k + 1, n_splits, dev)
         self.md_draft = AttentionMetadata(self.d_slots, self.block_tables, self.d_ctx, self.d_qstart, 1, n_splits)
         self.md_verify = AttentionMetadata(self.v_slots, self.block_tables, self.v_ctx, self.v_qstart, k + 1, n_splits)
-        self._graph: Optional[torch.cuda.CUDAGraph] = None
-        self._graph_draft: Optional[torch.cuda.CUDAGraph] = None   # fallback: proposer only (verify pass eager)
-        # ---- sampling parameters per slot (Sampler.forward's SamplingTensors, sampler.py:216-316).  temperature 0 = greedy
-        # (vLLM resets top_k / top_p of such requests itself, sampling_params.py).  While every occupied slot is greedy the
-        # cycle is the greedy one above (fused lm_head + softmax); as soon as one is not, the cycle samples EVERY row through
-        # ops.sample_top_k_top_p (greedy rows take the argmax there) -- a second captured graph, same state, same RNG stream
-        self.samp_temp = torch.zeros(B, dtype=torch.float32, device=dev)
-        self.samp_topk = torch.full((B,), -1, dtype=torch.int32, device=dev)
-        self.samp_topp = torch.ones(B, dtype=torch.float32, device=dev)
-        self.v_samp_temp = torch.zeros(T, dtype=torch.float32, device=dev)     # the same, one row per verify token
-        self.v_samp_topk = torch.full((T,), -1, dtype=torch.int32, device=dev)
-        self.v_samp_topp = torch.ones(T, dtype=torch.float32, device=dev)
-        self._samp_host = [(0.0, -1, 1.0)] * B
-        # per-request seeds (SamplingParams.seed): a seeded sampled request draws from Philox keyed by (seed, seq_lens at the
-        # start of the cycle, stream, j, v) alone -- the same tokens whatever slot it holds and whoever shares the batch
-        # (include/qspec_hip.h, "seeded draws").  seq_seeded[b] == 0: the engine stream (rng_state), as before
-        self.seq_seed = torch.zeros(B, dtype=i64, device=dev)
-        self.seq_seeded = torch.zeros(B, dtype=i32, device=dev)
-        self._seed_host: List[Optional[int]] = [None] * B
+        # ---- what the requests' SamplingParams become on the device (slot_sampling.py) and the mode level the occupied slots ask
+        # for: 0 greedy -- the cycle above (fused lm_head + softmax); 1 sampling -- EVERY row goes through ops.sample_top_k_top_p;
+        # 2 logit processors -- + the token-table catch-up and the logits pre-pass; 3 token constraints -- the pre-pass's constrained
+        # entry (same launches).  One captured cycle per level a batch has asked for, keyed (level, "full"), or (level, "draft"):
+        # the fallback, the proposer alone with the verify pass eager.  Every other batch replays what it always did.
+        self.sampling = SlotSampling(B, k, V, dev)
+        self._level = 0
+        self._graphs: dict = {}
         # the sampling front end's histogram workspaces (draft / non-speculative rows, verify rows), zero-filled here --
         # outside any capture -- and left zeroed by every call
         self._sample_ws_d = ops.new_sample_workspace(B, dev)
         self._sample_ws_v = ops.new_sample_workspace(T, dev)
-        self._mode_sampling = False
-        self._graph_s: Optional[torch.cuda.CUDAGraph] = None       # the cycle with the sampling front end
-        self._graph_draft_s: Optional[torch.cuda.CUDAGraph] = None
-        # ---- logit processors per slot (the rest of Sampler.forward, sampler.py:258-278): min_p, presence / frequency /
-        # repetition penalties, min_tokens.  Device arrays read at replay; penalties in fp16, the dtype the reference holds
-        # them in.  While no occupied slot has a non-neutral value the engine replays exactly the two cycles above; as soon
-        # as one has, it replays a THIRD captured cycle: the sampling cycle with the token-table catch-up at its head and the
-        # logits pre-pass (ops.process_logits) in front of every sampler call.  Every row is processed as the non-speculative
-        # sampler would process that position: prompt, committed outputs + the in-flight draft tokens d_1 .. d_j, generated
-        # length committed + j (include/qspec_hip.h, "logit processors").
-        # All of it is allocated on first use (_ensure_processing; an engine that never sees such a request holds none of
-        # it): the per-slot parameter arrays, the token table [B, V] (bit 31: in the prompt, low bits: output count),
-        # counted_len [B] (how many of gen_tokens[b][:gen_lens[b]] the table holds) and the processed-logits buffers.
-        # INVARIANT: the catch-up at the head of a cycle is driven by gen_lens alone, so recover() -- which restores gen_lens
-        # to the value it had at the start of the failed cycle, i.e. to counted_len -- re-runs it without double counting
-        self._lp_host = None                                       # per slot (min_p, pres, freq, rep, min_tokens, stop ids)
-        self.tok_table = None
-        self._mode_processing = False
-        self._graph_p: Optional[torch.cuda.CUDAGraph] = None       # the sampling cycle with the logit processors
-        self._graph_draft_p: Optional[torch.cuda.CUDAGraph] = None
-        # ---- token constraints per slot: logit_bias, allowed_token_ids, bad words (what the reference's engine lowers to logits
-        # processors in front of Sampler.forward; include/qspec_hip.h, "token constraints").  Device arrays (ops.TokenConstraints:
-        # a deny bitmask, a sorted bias list, the multi-token words, the pre-admission tail) allocated on first use and read at
-        # replay.  While an occupied slot carries one, the engine replays a FOURTH captured cycle: the processed cycle with the
-        # constrained pre-pass entry in place of the plain one (same launches).  Every other batch replays what it always did.
-        self._tc_host = None                                       # per slot None, or (biases, allowed ids, bad words)
-        self.tc = None
-        self._mode_constrained = False
-        self._graph_c: Optional[torch.cuda.CUDAGraph] = None       # the processed cycle with the token constraints
-        self._graph_draft_c: Optional[torch.cuda.CUDAGraph] = None
         # test hooks: injected random draws for the rejection sampler (eager mode only)
         self.inject_uniform: Optional[torch.Tensor] = None
         self.inject_exponential: Optional[torch.Tensor] = None
         self._prefill_scratch: Optional[Scratch] = None
 
-    _LP_NEUTRAL = (0.0, 0.0, 0.0, 1.0, 0, ())   # min_p, presence, frequency, repetition, min_tokens, stop ids
-    _lp_host: Optional[list] = None             # None until a request first uses a logit processor
-    tok_table: Optional[torch.Tensor] = None
-    _mode_processing = False
-    _tc_host: Optional[list] = None             # None until a request first carries a token constraint
-    tc = None
-    _mode_constrained = False
-    _graph_c = None
-    _graph_draft_c = None
-
-    def _lp(self, slot: int):
-        return self._LP_NEUTRAL if self._lp_host is None else self._lp_host[slot]
-
-    def _tc(self, slot: int):
-        return None if self._tc_host is None else self._tc_host[slot]
+    # names the benchmark, scripts and tests read: whole-cycle graph per level, draft-only fallback, modes, state of self.sampling
+    _graph, _graph_s, _graph_p, _graph_c = (property(lambda self, lv=lv: self._graphs.get((lv, "full"))) for lv in range(4))
+    _graph_draft = property(lambda self: self._graphs.get((0, "draft")))
+    _mode_sampling, _mode_processing, _mode_constrained = (property(lambda self, lv=lv: self._level >= lv) for lv in (1, 2, 3))
+    seq_seeded, lp_gen_base, tok_table, counted_len, proc_logits_d, proc_logits_v, tc, _lp_host, _tc_host = (
+        property(lambda self, n=n: getattr(self.sampling, n)) for n in
+        "seq_seeded lp_gen_base tok_table counted_len proc_logits_d proc_logits_v tc _lp_host _tc_host".split())
 
     # the embedding lookups of the cycle's four forwards ride in the bookkeeping launches in front of them (5 launches less)
     EMBED_IN_BOOKKEEPING = os.environ.get("QSPEC_EMBED_IN_BOOKKEEPING", "1") != "0"
@@ -310,21 +262,9 @@ class QSpecEngine:
                                torch.tensor(lens, dtype=torch.int32, device=dev), q_start, Tmax, 1)
         hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False, **self._kv_fw)
         last = (q_start[1:].long() - 1)
-        logits = self.model.compute_logits(hs[last].contiguous(), s)
-        probs = torch.empty(n, cfg.vocab_size, dtype=torch.float32, device=dev)
-        tok = torch.empty(n, dtype=torch.int64, device=dev)
         for i, b in enumerate(slots):
-            self._admit_tokens(b, prompts[i], npts[i])
-        self._first_token(logits, probs, tok, list(slots), lens)
-        for i, (b, T) in enumerate(zip(slots, lens)):
-            self.seq_lens[b] = T + 1
-            self.last_token[b] = tok[i]
-            self.gen_tokens[b].fill_(-1)
-            self.gen_tokens[b, 0] = tok[i]
-            self.gen_lens[b] = 1
-            self._len_ub[b] = T + 1
-            self._gen_ub[b] = 1
-        self.n_active = sum(1 for v in self._len_ub if v > 0)
+            self.sampling.admit_tokens(b, prompts[i], npts[i])
+        self._first_token(hs[last].contiguous(), s, list(slots), lens)
         torch.cuda.synchronize()
 
     @torch.no_grad()
@@ -355,40 +295,58 @@ class QSpecEngine:
                                torch.tensor([T], dtype=torch.int32, device=dev),
                                torch.tensor([0, T], dtype=torch.int32, device=dev), T, n_splits_for(T))
         hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False, **self._kv_fw)
-        logits = self.model.compute_logits(hs[T - 1:T], s)
-        probs = torch.empty(1, cfg.vocab_size, dtype=torch.float32, device=dev)
-        tok = torch.empty(1, dtype=torch.int64, device=dev)
-        self._admit_tokens(b, prompt, num_prompt_tokens)
-        self._first_token(logits, probs, tok, [b], [T])
-        self.seq_lens[b] = T + 1
-        self.last_token[b] = tok[0]
-        self.gen_tokens[b].fill_(-1)
-        self.gen_tokens[b, 0] = tok[0]
-        self.gen_lens[b] = 1
-        self._len_ub[b] = T + 1
-        self._gen_ub[b] = 1
-        self.n_active = sum(1 for v in self._len_ub if v > 0)
+        self.sampling.admit_tokens(b, prompt, num_prompt_tokens)
+        self._first_token(hs[T - 1:T], s, [b], [T])
         if sync:
             torch.cuda.synchronize()
 
-    def _first_token(self, logits, probs, tok, slots: List[int], prompt_lens: List[int]) -> None:
-        """The target's first token of freshly admitted prompts: greedy, or sampled with the slots' parameters (a seeded
-        request: target stream, j = 0, base position = its prompt length)."""
-        constrained = any(self._tc(b) is not None for b in slots)
-        processed = constrained or any(self._lp(b) != self._LP_NEUTRAL for b in slots)
-        if processed:   # position 0 of the request: j = 0, no in-flight tokens (gen_lens of a fresh slot is 0)
-            logits = self._process(logits, torch.empty_like(logits), rows_per_seq=1, j_base=0, draft_ids=None, active_lens=None,
-                                   slot_ids=torch.tensor(slots, dtype=torch.int32, device=self.device), constrained=constrained)
-        if all(self._samp_host[b][0] < 1e-5 for b in slots):
-            ops.softmax_argmax(logits, probs, tok)
+    def _first_token(self, hs, scratch, slots: List[int], prompt_lens: List[int]) -> None:
+        """The target's first token of freshly admitted prompts (hs: their last hidden rows): greedy, or sampled with the
+        slots' parameters (a seeded request: target stream, j = 0, base position = its prompt length).  The mode comes from the
+        admitted slots alone; position 0 of a request has no in-flight tokens (gen_lens of a fresh slot is 0)."""
+        n, level, greedy = len(slots), self.sampling.level(slots), not self.sampling.sampling_on(slots)
+        probs = torch.empty(n, self.cfg.vocab_size, dtype=torch.float32, device=self.device)
+        tok = torch.empty(n, dtype=torch.int64, device=self.device)
+        rows = self.sampling.gathered_rows(slots, level, not greedy, scratch.logits[:n])
+        base_pos = None if greedy else torch.tensor(prompt_lens, dtype=torch.int32, device=self.device)
+        self._sample(level, rows, hs, scratch, probs, tok, base_pos=base_pos, argmax=greedy)
+        for i, (b, T) in enumerate(zip(slots, prompt_lens)):   # the slots are occupied from here on
+            self.seq_lens[b] = T + 1
+            self.last_token[b] = tok[i]
+            self.gen_tokens[b].fill_(-1)
+            self.gen_tokens[b, 0] = tok[i]
+            self.gen_lens[b] = 1
+            self._len_ub[b] = T + 1
+            self._gen_ub[b] = 1
+        self.n_active = sum(1 for v in self._len_ub if v > 0)
+
+    def _sample(self, level: int, rows, hs, scratch, probs, token, base_pos, rows_per_seq: int = 1, j_base: int = 0,
+                draw_stream: int = 2, active_lens=None, draft_ids=None, workspace=None, shard_vocab: bool = False, hook=None,
+                fused_greedy: bool = False, argmax: bool = False) -> None:
+        """THE sampling front end -- the first token, the non-speculative step, every draft step and the verify pass come through
+        here: lm_head -> the bench-only hook -> from level 2 on the logits pre-pass (self._process, out of place: the raw logits
+        stay in scratch.logits; level 3: its constrained entry) -> ops.sample_top_k_top_p over EVERY row (greedy rows take the
+        argmax there; min_p from level 2 on), or with `argmax` ops.softmax_argmax.  probs [T, V] fp32 is the
+        PROCESSED distribution: what the rejection sampler must see.  rows: the per-row arrays (SlotSampling.draft_rows /
+        verify_rows / gathered_rows); row t belongs to sequence t // rows_per_seq and is position j_base + t % rows_per_seq of
+        its cycle; draw_stream: 1 draft, 2 target; base_pos: the seeded draws' base position per sequence.  fused_greedy: level 0
+        may take the fused lm_head + softmax launch (model.sample_greedy decides; same bits)."""
+        if level == 0 and fused_greedy:
+            self.model.sample_greedy(hs, scratch, probs, token, shard_vocab=shard_vocab, logits_hook=hook)
             return
-        idx = torch.tensor(slots, dtype=torch.int64, device=self.device)
-        ops.sample_top_k_top_p(logits, probs, tok, self.samp_temp[idx].contiguous(), self.samp_topk[idx].contiguous(),
-                               self.samp_topp[idx].contiguous(), rng_state=self.sampler.rng_state,
-                               min_p=self.samp_minp[idx].contiguous() if processed else None,
-                               seq_seeds=self.seq_seed[idx].contiguous(), seq_seeded=self.seq_seeded[idx].contiguous(),
-                               base_pos=torch.tensor(prompt_lens, dtype=torch.int32, device=self.device),
-                               rows_per_seq=1, j_base=0, draw_stream=2)
+        logits = self.model.compute_logits(hs, scratch, shard_vocab=shard_vocab)
+        if hook is not None:
+            hook(logits)
+        if level >= 2:
+            logits = self._process(logits, rows.proc_out, rows_per_seq, j_base, draft_ids, active_lens, slot_ids=rows.slot_ids,
+                                   constrained=level == 3)
+        if argmax:
+            ops.softmax_argmax(logits, probs, token)
+        else:
+            ops.sample_top_k_top_p(logits, probs, token, rows.temp, rows.topk, rows.topp, rng_state=self.sampler.rng_state,
+                                   workspace=workspace, min_p=rows.minp if level >= 2 else None, seq_seeds=rows.seeds,
+                                   seq_seeded=rows.seeded, base_pos=base_pos, rows_per_seq=rows_per_seq, j_base=j_base,
+                                   draw_stream=draw_stream)
 
     def free_slot(self, slot: int) -> None:
         """The request in `slot` has finished (EOS / max_tokens / aborted): the slot goes back to empty."""
@@ -432,193 +390,15 @@ class QSpecEngine:
         BEFORE admission.  Refused with ValueError, nothing enqueued: an id outside the vocabulary, an empty allowed set or
         bad word, a cap exceeded, a non-finite bias, an occupied slot, and a request that can never emit anything (every
         allowed token is a single-token bad word -- or, with min_tokens, a stop id)."""
-        stop = tuple(int(t) for t in stop_token_ids)
-        vals = (float(min_p), float(presence_penalty), float(frequency_penalty), float(repetition_penalty))
-        if len(stop) > ops.MAX_STOP_IDS:
-            raise ValueError(f"{len(stop)} stop token ids: at most {ops.MAX_STOP_IDS} are supported")
-        if not all(v == v and abs(v) != float("inf") for v in vals):
-            raise ValueError("min_p and the penalties must be finite")
-        if not 0.0 <= vals[0] <= 1.0:
-            raise ValueError(f"min_p {min_p} outside [0, 1]")
-        if not vals[3] > 0.0:
-            raise ValueError(f"repetition_penalty {repetition_penalty} must be > 0")
-        if int(min_tokens) < 0:
-            raise ValueError(f"min_tokens {min_tokens} must be >= 0")
-        want_tc = self._validate_constraints(slot, logit_bias, allowed_token_ids, bad_words_token_ids,
-                                             stop if int(min_tokens) > 0 else ())
-        if temperature < 1e-5:   # (min_p is reset for greedy requests, sampling_params.py:344; the rest applies to them too)
-            temperature, top_k, top_p, seed = 0.0, -1, 1.0, None
-            vals = (0.0,) + vals[1:]
-        if int(min_tokens) == 0 or not stop:
-            min_tokens, stop = 0, ()
-        want_lp = vals + (int(min_tokens), stop)
-        if want_lp != self._lp(slot):
-            h = torch.tensor(vals[1:], dtype=torch.float16)   # what the kernels will read
-            if float(h[2]) <= 0.0 or not bool(torch.isfinite(h).all()):
-                raise ValueError("a penalty is outside the fp16 range")
-            need = int(float(h[0]) != 0.0 or float(h[1]) != 0.0 or float(h[2]) != 1.0)
-            if need and self._len_ub[slot] > 0 and not self._lp_needs(slot):
-                raise ValueError(f"slot {slot} is occupied: penalties are set before the request is admitted (its token "
-                                 "table is built at admission)")
-            self._ensure_processing()
-            k1 = self.k + 1
-            self.samp_minp[slot] = vals[0]
-            self.v_samp_minp[slot * k1:(slot + 1) * k1] = vals[0]
-            self.lp_pres[slot] = h[0]; self.lp_freq[slot] = h[1]; self.lp_rep[slot] = h[2]
-            self.lp_min_tokens[slot] = int(min_tokens)
-            row = torch.zeros(ops.MAX_STOP_IDS, dtype=torch.int32)
-            if stop:
-                row[:len(stop)] = torch.tensor(stop, dtype=torch.int64).clamp(-1, 2 ** 31 - 1).to(torch.int32)
-            self.lp_stop_ids[slot].copy_(row.to(self.device))
-            self.lp_n_stop[slot] = len(stop)
-            self.lp_need[slot] = need
-            self._lp_host[slot] = want_lp
-        if want_tc != self._tc(slot):
-            self._ensure_processing()
-            self._ensure_constraints()
-            if want_tc is None:
-                ops.token_constraints_set(self.tc, slot)           # flags off: the slot is unconstrained again
-            else:
-                ops.token_constraints_set(self.tc, slot, dict(want_tc[0]), want_tc[1], [list(w) for w in want_tc[2]])
-            self._tc_host[slot] = want_tc
-        want_seed = None if seed is None else int(seed) % (1 << 64)
-        if self._seed_host[slot] != want_seed:
-            self.seq_seed[slot] = 0 if want_seed is None else want_seed - (1 << 64) * (want_seed >= 1 << 63)
-            self.seq_seeded[slot] = 0 if want_seed is None else 1
-            self._seed_host[slot] = want_seed
-        want = (float(temperature), int(top_k) if top_k and top_k > 0 else -1, float(top_p))
-        if self._samp_host[slot] == want:
-            return
-        k1 = self.k + 1
-        self.samp_temp[slot] = want[0]; self.samp_topk[slot] = want[1]; self.samp_topp[slot] = want[2]
-        self.v_samp_temp[slot * k1:(slot + 1) * k1] = want[0]
-        self.v_samp_topk[slot * k1:(slot + 1) * k1] = want[1]
-        self.v_samp_topp[slot * k1:(slot + 1) * k1] = want[2]
-        self._samp_host[slot] = want
-
-    def _validate_constraints(self, slot: int, logit_bias, allowed_token_ids, bad_words_token_ids, stop: Sequence[int]):
-        """The canonical form of a request's token constraints -- (sorted (id, bias) pairs, sorted allowed ids or None, bad
-        words) -- or None when it has none.  Raises ValueError; enqueues nothing."""
-        if not logit_bias and allowed_token_ids is None and not bad_words_token_ids:
-            return None
-        V = self.cfg.vocab_size
-        try:
-            bias = {int(t): float(b) for t, b in (logit_bias or {}).items()}
-        except (TypeError, ValueError) as exc:
-            raise ValueError("logit_bias maps token ids (integers or strings of integers) to numbers") from exc
-        allowed = None if allowed_token_ids is None else tuple(sorted(set(int(t) for t in allowed_token_ids)))
-        words = []
-        for w in (bad_words_token_ids or ()):
-            w = tuple(int(t) for t in w)
-            if not w:
-                raise ValueError("an empty bad word")
-            if w not in words:
-                words.append(w)
-        if allowed is not None and not allowed:
-            raise ValueError("Empty allowed_token_ids provided")
-        for name, ids in (("logit_bias", bias), ("allowed_token_ids", allowed or ()), ("bad_words_token_ids", [t for w in words for t in w])):
-            bad = [t for t in ids if not 0 <= t < V]
-            if bad:
-                raise ValueError(f"{name} contains out-of-vocab token ids {bad[:8]} (vocabulary size {V})")
-        if not all(b == b and abs(b) != float("inf") for b in bias.values()):
-            raise ValueError("a logit_bias value is not finite")
-        multi = [w for w in words if len(w) > 1]
-        if len(bias) > ops.MAX_LOGIT_BIAS:
-            raise ValueError(f"{len(bias)} logit_bias entries: at most {ops.MAX_LOGIT_BIAS} are supported")
-        if len(multi) > ops.MAX_BAD_WORDS:
-            raise ValueError(f"{len(multi)} multi-token bad words: at most {ops.MAX_BAD_WORDS} are supported")
-        if any(len(w) > ops.MAX_BAD_WORD_LEN for w in multi):
-            raise ValueError(f"a bad word is longer than {ops.MAX_BAD_WORD_LEN} tokens")
-        single = set(w[0] for w in words if len(w) == 1)
-        left = (set(allowed) if allowed is not None else None)
-        n_left = len(left - single) if left is not None else V - len(single)
-        if n_left <= 0:
-            raise ValueError("every allowed token is a single-token bad word: the request could never emit a token")
-        if stop:
-            gone = single | set(int(t) for t in stop if 0 <= int(t) < V)
-            if (len(left - gone) if left is not None else V - len(gone)) <= 0:
-                raise ValueError("before min_tokens every allowed token is a bad word or a stop id: the request could never "
-                                 "emit a token")
-        want = (tuple(sorted(bias.items())), allowed, tuple(words))
-        if want != self._tc(slot) and self._len_ub[slot] > 0:
-            raise ValueError(f"slot {slot} is occupied: token constraints are set before the request is admitted")
-        return want
-
-    def _constraints_on(self) -> bool:
-        """Some occupied slot carries a token constraint: the cycle is the fourth graph."""
-        return self._tc_host is not None and any(self._tc_host[b] is not None for b in range(self.B) if self._len_ub[b] > 0)
-
-    def _ensure_constraints(self) -> None:
-        if self._tc_host is None:
-            self.tc = ops.TokenConstraints(self.B, self.cfg.vocab_size, self.device)
-            self._tc_host = [None] * self.B
-
-    def _sampling_on(self) -> bool:
-        return any(self._samp_host[b][0] >= 1e-5 for b in range(self.B) if self._len_ub[b] > 0)
-
-    def _processing_on(self) -> bool:
-        """Some occupied slot has a non-neutral logit-processor value: the cycle is the third graph."""
-        return self._constraints_on() or (self._lp_host is not None and any(
-            self._lp_host[b] != self._LP_NEUTRAL for b in range(self.B) if self._len_ub[b] > 0))
-
-    def _lp_needs(self, slot: int) -> bool:
-        """The slot keeps token counts: one of its penalties is non-neutral (in fp16, as the kernels read it)."""
-        _, pres, freq, rp, _, _ = self._lp(slot)
-        h = torch.tensor((pres, freq, rp), dtype=torch.float16)
-        return bool(float(h[0]) != 0.0 or float(h[1]) != 0.0 or float(h[2]) != 1.0)
-
-    def _ensure_processing(self) -> None:
-        if self._lp_host is not None:
-            return
-        B, T, V, dev, i32 = self.B, self.B * (self.k + 1), self.cfg.vocab_size, self.device, torch.int32
-        self.samp_minp = torch.zeros(B, dtype=torch.float32, device=dev)
-        self.v_samp_minp = torch.zeros(T, dtype=torch.float32, device=dev)     # the same, one row per verify token
-        self.lp_rep = torch.ones(B, dtype=torch.float16, device=dev)
-        self.lp_freq = torch.zeros(B, dtype=torch.float16, device=dev)
-        self.lp_pres = torch.zeros(B, dtype=torch.float16, device=dev)
-        self.lp_min_tokens = torch.zeros(B, dtype=i32, device=dev)
-        self.lp_gen_base = torch.zeros(B, dtype=i32, device=dev)   # outputs a re-admitted request had before its admission
-        self.lp_stop_ids = torch.zeros(B, ops.MAX_STOP_IDS, dtype=i32, device=dev)
-        self.lp_n_stop = torch.zeros(B, dtype=i32, device=dev)
-        self.lp_need = torch.zeros(B, dtype=i32, device=dev)       # the slot keeps token counts (a non-neutral penalty)
-        self._gen_base_host = [0] * B
-        self.tok_table, self.counted_len = ops.new_logit_table(B, V, dev)
-        self.proc_logits_d = torch.zeros(B, V, dtype=torch.float16, device=dev)   # draft steps / non-speculative step
-        self.proc_logits_v = torch.zeros(T, V, dtype=torch.float16, device=dev)   # verify rows
-        self._lp_host = [self._LP_NEUTRAL] * B
-
-    def _admit_tokens(self, slot: int, tokens: Sequence[int], num_prompt_tokens: Optional[int]) -> None:
-        """Admission: the outputs the request already has (recomputation), for a slot with penalties its table row, for a slot
-        with token constraints the tail of those outputs (a bad word may straddle the admission)."""
-        if self._lp_host is None:
-            return
-        npt = len(tokens) if num_prompt_tokens is None else int(num_prompt_tokens)
-        base = len(tokens) - npt
-        if self._tc(slot) is not None:
-            ops.token_constraints_set_tail(self.tc, slot, list(tokens)[npt:])
-        if self._gen_base_host[slot] != base:
-            self.lp_gen_base[slot] = base
-            self._gen_base_host[slot] = base
-        if self._lp_needs(slot):
-            ids = torch.tensor(list(tokens), dtype=torch.int64, device=self.device)
-            ops.logit_table_set_prompt(self.tok_table, self.counted_len, slot, ids[:npt].contiguous(),
-                                       ids[npt:].contiguous() if base else None)
+        self.sampling.set(slot, temperature, top_k, top_p, seed, min_p, presence_penalty, frequency_penalty, repetition_penalty,
+                          min_tokens, stop_token_ids, logit_bias, allowed_token_ids, bad_words_token_ids,
+                          occupied=self._len_ub[slot] > 0)
 
     def _process(self, logits, out, rows_per_seq: int, j_base: int, draft_ids, active_lens, slot_ids=None,
                  constrained: Optional[bool] = None):
-        T = logits.shape[0]
-        if self._mode_constrained if constrained is None else constrained:
-            return ops.process_logits_constrained(logits, out[:T], self.tok_table, self.lp_rep, self.lp_freq, self.lp_pres,
-                                                  self.lp_min_tokens, self.lp_gen_base, self.gen_lens, self.lp_stop_ids,
-                                                  self.lp_n_stop, *self.tc.arrays(), self.gen_tokens, draft_ids=draft_ids,
-                                                  rows_per_seq=rows_per_seq, j_base=j_base, slot_ids=slot_ids,
-                                                  active_lens=active_lens)
-        return ops.process_logits(logits, out[:T], self.tok_table, self.lp_rep, self.lp_freq, self.lp_pres, self.lp_min_tokens,
-                                  self.lp_gen_base, self.gen_lens, self.lp_stop_ids, self.lp_n_stop, draft_ids=draft_ids,
-                                  rows_per_seq=rows_per_seq, j_base=j_base, slot_ids=slot_ids, active_lens=active_lens)
-
-    def _catch_up(self) -> None:
-        ops.logit_table_catch_up(self.tok_table, self.counted_len, self.lp_need, self.gen_tokens, self.gen_lens)
+        """The logits pre-pass of the front end (tests wrap it on the instance: it is looked up at call time)."""
+        return self.sampling.process(logits, out, rows_per_seq, j_base, draft_ids, active_lens, self.gen_tokens, self.gen_lens,
+                                     slot_ids=slot_ids, constrained=self._level == 3 if constrained is None else constrained)
 
     def set_block_table(self, slot: int, blocks: Sequence[int]) -> None:
         """The scheduler's block table of the request in `slot` (vLLM SequenceGroupMetadata.block_tables); it must
@@ -686,8 +466,8 @@ class QSpecEngine:
 
     def _cycle_head(self):
         self._snapshot()
-        if self._mode_processing:   # the tokens committed since the last catch-up enter the table (idempotent: see __init__)
-            self._catch_up()
+        if self._level >= 2:   # the tokens committed since the last catch-up enter the table (idempotent: slot_sampling.py)
+            self.sampling.catch_up(self.gen_tokens, self.gen_lens)
 
     def _cycle_body(self):
         self._cycle_head()
@@ -728,16 +508,10 @@ class QSpecEngine:
         for i in range(k):
             hs = m.forward(self.d_tokens, self.d_pos, self.kv_caches, self.md_draft, self.scratch_draft, w4a4=True,
                            embedded=emb_d is not None, **self._kv_fw)
-            if self._mode_sampling:   # draft tokens are SAMPLED from the processed draft distribution (sampler.py:216-316)
-                extra = {}
-                if self._mode_processing:   # draft step i proposes d_{i+1}: it sees d_1 .. d_i in flight
-                    extra = dict(min_p=self.samp_minp, process=lambda lg, j=i: self._process(
-                        lg, self.proc_logits_d, 1, j, self.draft_ids_kb, self.eff_lens))
-                m.sample(hs, self.scratch_draft, self.draft_probs_kbv[i], self.draft_ids_kb[i], self.samp_temp, self.samp_topk,
-                         self.samp_topp, self.sampler.rng_state, shard_vocab=draft_sv, workspace=self._sample_ws_d,
-                         **extra, **self._seed_args(rows_per_seq=1, j_base=i, draw_stream=1))
-            else:
-                m.sample_greedy(hs, self.scratch_draft, self.draft_probs_kbv[i], self.draft_ids_kb[i], shard_vocab=draft_sv)
+            # (from level 1 on SAMPLED from the processed draft distribution, sampler.py:216-316; step i sees d_1 .. d_i in flight)
+            self._sample(self._level, self.sampling.draft_rows(), hs, self.scratch_draft, self.draft_probs_kbv[i],
+                         self.draft_ids_kb[i], base_pos=self.seq_lens, j_base=i, draw_stream=1, active_lens=self.eff_lens,
+                         draft_ids=self.draft_ids_kb, workspace=self._sample_ws_d, shard_vocab=draft_sv, fused_greedy=True)
             if i != k - 1:  # _gpu_advance_step (draft_model_runner.py:78-135)
                 ops.spec_advance_draft(bs, self.d_tokens, self.draft_ids_kb[i], self.d_pos, self.d_ctx, self.d_slots,
                                        self.block_tables, embed=emb_d)
@@ -752,32 +526,21 @@ class QSpecEngine:
                                 self.v_pos, self.v_slots, self.v_ctx, embed=emb_v)
         hs = m.forward(self.v_tokens, self.v_pos, self.kv_caches, self.md_verify, self.scratch_verify, w4a4=False,
                        embedded=emb_v is not None, **self._kv_fw)
-        hook = self._verify_logits_hook(draft_ids)
-        seeded = {}
-        if self._mode_sampling:
-            extra = {}
-            if self._mode_processing:   # verify row j = 0..k sees d_1 .. d_j in flight
-                extra = dict(min_p=self.v_samp_minp, process=lambda lg: self._process(
-                    lg, self.proc_logits_v, k + 1, 0, self.draft_ids_kb, self.eff_lens))
-            m.sample(hs, self.scratch_verify, self.target_probs.view(B * (k + 1), -1), self.target_tokens.view(-1),
-                     self.v_samp_temp, self.v_samp_topk, self.v_samp_topp, self.sampler.rng_state, shard_vocab=True,
-                     logits_hook=hook, workspace=self._sample_ws_v, **extra,
-                     **self._seed_args(rows_per_seq=k + 1, j_base=0, draw_stream=2))
-            seeded = self._seed_args()
-        else:
-            m.sample_greedy(hs, self.scratch_verify, self.target_probs.view(B * (k + 1), -1), self.target_tokens.view(-1),
-                            shard_vocab=True, logits_hook=hook)
+        # verify row j = 0..k sees d_1 .. d_j in flight
+        self._sample(self._level, self.sampling.verify_rows(), hs, self.scratch_verify, self.target_probs.view(B * (k + 1), -1),
+                     self.target_tokens.view(-1), base_pos=self.seq_lens, rows_per_seq=k + 1, active_lens=self.eff_lens,
+                     draft_ids=self.draft_ids_kb, workspace=self._sample_ws_v, shard_vocab=True,
+                     hook=self._verify_logits_hook(draft_ids), fused_greedy=True)
+        # the rejection sampler's own draws are seeded per sequence in the sampling modes only; base position = seq_lens at the
+        # start of the cycle (read on the device at replay, restored by recover(), so a replayed cycle repeats its draws)
+        seeded = dict(seq_seeds=self.sampling.seq_seed, seq_seeded=self.sampling.seq_seeded, base_pos=self.seq_lens) \
+            if self._level >= 1 else {}
         # _verify_tokens (:861-970): bonus = the target's own token at the last position
         self.sampler.forward(self.target_probs, self.target_tokens[:, k], draft_probs, draft_ids, out=self.out_tokens,
                              accepted=self.accepted, recovered=self.recovered, uniform=self.inject_uniform,
                              exponential=self.inject_exponential, active_lens=self.eff_lens, **seeded)
         # _create_output_sampler_list bookkeeping (:972-1063)
         ops.spec_commit(self.out_tokens, self.seq_lens, self.last_token, self.gen_tokens, self.gen_lens)
-
-    def _seed_args(self, **rows) -> dict:
-        """The per-sequence seed arguments of the sampling calls: base position = seq_lens at the start of the cycle
-        (read on the device at replay, restored by recover(), so a replayed cycle repeats its draws)."""
-        return dict(seq_seeds=self.seq_seed, seq_seeded=self.seq_seeded, base_pos=self.seq_lens, **rows)
 
     @torch.no_grad()
     def _verify_logits_hook(self, draft_ids):
@@ -806,18 +569,12 @@ class QSpecEngine:
         ops.spec_prepare_draft(self.last_token, self.eff_lens, self.block_tables, bs, self.d_tokens, self.d_pos,
                                self.d_slots, self.d_ctx)                   # [last token] at position seq_len - 1
         hs = m.forward(self.d_tokens, self.d_pos, self.kv_caches, self.md_draft, self.scratch_draft, w4a4=False, **self._kv_fw)
-        logits = m.compute_logits(hs, self.scratch_draft)
-        processing = self._processing_on()
-        if processing:   # position j = 0, nothing in flight: catch up with the committed tokens, then the pre-pass
-            self._catch_up()
-            logits = self._process(logits, self.proc_logits_d, 1, 0, None, self.eff_lens, constrained=self._constraints_on())
-        if self._sampling_on() or processing:   # sampled requests sample (a seeded one: target stream, j = 0); greedy rows take the argmax
-            ops.sample_top_k_top_p(logits, self.draft_probs_kbv[0], self.draft_ids_kb[0], self.samp_temp, self.samp_topk,
-                                   self.samp_topp, rng_state=self.sampler.rng_state, workspace=self._sample_ws_d,
-                                   min_p=self.samp_minp if processing else None,
-                                   **self._seed_args(rows_per_seq=1, j_base=0, draw_stream=2))
-        else:
-            ops.softmax_argmax(logits, self.draft_probs_kbv[0], self.draft_ids_kb[0])
+        # the mode of ALL occupied slots; position j = 0, nothing in flight: catch up with the committed tokens, then the pre-pass
+        level = self.sampling.level(self.active_slots())
+        if level >= 2:
+            self.sampling.catch_up(self.gen_tokens, self.gen_lens)
+        self._sample(level, self.sampling.draft_rows(), hs, self.scratch_draft, self.draft_probs_kbv[0], self.draft_ids_kb[0],
+                     base_pos=self.seq_lens, active_lens=self.eff_lens, workspace=self._sample_ws_d, argmax=level == 0)
         self.out_tokens.fill_(-1)
         self.out_tokens[:, 0] = torch.where(self.eff_lens > 0, self.draft_ids_kb[0], torch.full_like(self.draft_ids_kb[0], -1))
         ops.spec_commit(self.out_tokens, self.seq_lens, self.last_token, self.gen_tokens, self.gen_lens)
@@ -836,20 +593,18 @@ class QSpecEngine:
         for b in on:                       # until the caller reports / syncs the real numbers: the worst case
             self._len_ub[b] += self.k + 1
             self._gen_ub[b] += self.k + 1
-        # (every rank sees the same requests: the same decisions.)  The processed cycle is the sampling cycle + the pre-pass
-        self._mode_constrained = self._constraints_on()
-        self._mode_processing = self._processing_on()
-        self._mode_sampling = self._mode_processing or self._sampling_on()
+        # (every rank sees the same requests: the same decisions)
+        level = self._level = self.sampling.level(self.active_slots())
         if not self.use_graph:
             self._cycle_body()
             return
-        full, draft = self._graphs()
+        full, draft = self._graphs.get((level, "full")), self._graphs.get((level, "draft"))
         if full is None and draft is None:
             self._capture()
             if not self.use_graph:
                 self._cycle_body()
                 return
-            full, draft = self._graphs()
+            full, draft = self._graphs.get((level, "full")), self._graphs.get((level, "draft"))
         if full is not None:
             full.replay()
         else:   # the verify pass could not be captured (its collectives): proposer from its graph, scorer eagerly.
@@ -859,61 +614,42 @@ class QSpecEngine:
             self._verify_body()
             self._collect_errors()
 
-    def _graph_names(self):
-        return ("_graph_c", "_graph_draft_c") if self._mode_constrained else \
-            ("_graph_p", "_graph_draft_p") if self._mode_processing else \
-            ("_graph_s", "_graph_draft_s") if self._mode_sampling else ("_graph", "_graph_draft")
-
-    def _graphs(self):
-        """(whole-cycle graph, draft-only graph) of the current mode: greedy, sampling, processed or constrained."""
-        full, draft = self._graph_names()
-        return getattr(self, full), getattr(self, draft)
-
     def _capture(self):
+        """Capture the cycle of the current level: the whole cycle, else the draft pass alone (verify eager), else eager."""
+        import gc
+        import warnings
         # warm up outside capture (lazy module loads, LDS attribute), on a side stream as torch requires.
-        # The warm-up cycles advance the sequence state; restore it so capture does not consume tokens.
-        state = [t.clone() for t in (self.seq_lens, self.last_token, self.gen_tokens, self.gen_lens,
-                                     self.sampler.counters, self.sampler.rng_state)]
+        # The warm-up cycle advances the sequence state; restore it so capture does not consume tokens.
+        live = (self.seq_lens, self.last_token, self.gen_tokens, self.gen_lens, self.sampler.counters, self.sampler.rng_state)
+        state = [t.clone() for t in live]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             self._cycle_body()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        import gc
         gc.collect()   # no stale CUDAGraph may be finalised while this capture is under way
         try:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 self._cycle_body()
-            torch.cuda.synchronize()
+            self._graphs[(self._level, "full")] = g
         except Exception as exc:  # e.g. a collective backend that cannot be captured: loudly, not silently
-            import warnings
             torch.cuda.synchronize()
-            for t, s in zip((self.seq_lens, self.last_token, self.gen_tokens, self.gen_lens, self.sampler.counters,
-                             self.sampler.rng_state), state):
-                t.copy_(s)
             try:   # the proposer has no collectives (replicated under TP): keep its k forwards in a graph
                 gd = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gd):
                     self._cycle_head()
                     self._draft_body()
-                torch.cuda.synchronize()
-                setattr(self, self._graph_names()[1], gd)
+                self._graphs[(self._level, "draft")] = gd
                 warnings.warn(f"hipGraph capture of the whole cycle failed ({exc!r}); "
                               "the draft pass replays from a graph, the verify pass runs eagerly")
             except Exception as exc2:
                 warnings.warn(f"hipGraph capture failed ({exc!r}; draft only: {exc2!r}); running the cycle eagerly")
                 self.use_graph = False
-                torch.cuda.synchronize()
-            for t, s in zip((self.seq_lens, self.last_token, self.gen_tokens, self.gen_lens, self.sampler.counters,
-                             self.sampler.rng_state), state):
-                t.copy_(s)
-            return
-        for t, s in zip((self.seq_lens, self.last_token, self.gen_tokens, self.gen_lens, self.sampler.counters,
-                         self.sampler.rng_state), state):
+        torch.cuda.synchronize()
+        for t, s in zip(live, state):   # every exit path: the sequence state of before the warm-up
             t.copy_(s)
-        setattr(self, self._graph_names()[0], g)
 
     # ------------------------------------------------------------------ results
     def generated(self) -> List[List[int]]:

@@ -15,7 +15,7 @@ import logit_cases as lc  # noqa: E402
 
 from qspec_amd import _lib  # noqa: E402
 from qspec_amd.spec_decode import worker as W  # noqa: E402
-from qspec_amd.spec_decode.engine import QSpecEngine  # noqa: E402
+from host_engine import HostEngine  # noqa: E402
 
 NEW = ("qspec_process_logits", "qspec_logit_table_set_prompt", "qspec_logit_table_catch_up",
        "qspec_sample_top_k_top_p_min_p", "qspec_sample_top_k_top_p_min_p_seeded")
@@ -124,57 +124,40 @@ def test_new_symbols_declared_bound_exported_and_validating():
     assert rc != 0 and b"does not cover" in lib.qspec_last_error()
 
 
-class _HostEngine(QSpecEngine):
-    """QSpecEngine's slot bookkeeping on host tensors (no model, no GPU)."""
-
-    def __init__(self, B=4, k=3):
-        self.k, self.B, self.device = k, B, torch.device("cpu")
-        self.cfg = SimpleNamespace(vocab_size=64)
-        self.blocks_per_seq, self.block_size, self.num_blocks = 16, 16, B * 16
-        T = B * (k + 1)
-        self.seq_lens = torch.zeros(B, dtype=torch.int32)
-        self.gen_lens = torch.zeros(B, dtype=torch.int32)
-        self._len_ub, self._gen_ub, self._bt_host = [0] * B, [0] * B, [None] * B
-        self.samp_temp, self.samp_topk, self.samp_topp = torch.zeros(B), torch.full((B,), -1, dtype=torch.int32), torch.ones(B)
-        self.v_samp_temp, self.v_samp_topk, self.v_samp_topp = torch.zeros(T), torch.full((T,), -1, dtype=torch.int32), torch.ones(T)
-        self._samp_host = [(0.0, -1, 1.0)] * B
-        self.seq_seed = torch.zeros(B, dtype=torch.int64)
-        self.seq_seeded = torch.zeros(B, dtype=torch.int32)
-        self._seed_host = [None] * B
-
-
 def test_engine_slot_arrays_follow_set_sampling_params_and_free_slot():
-    eng = _HostEngine()
+    eng = HostEngine()
+    s = eng.sampling
     eng.set_sampling_params(1, 0.8, 50, 0.9)                      # nothing new asked for: nothing new allocated
-    assert eng._lp_host is None and eng.tok_table is None and not eng._processing_on()
+    assert s._lp_host is None and s.tok_table is None and not s.processing_on(eng.active_slots())
     eng.set_sampling_params(2, 0.8, min_p=0.05, repetition_penalty=1.2, frequency_penalty=0.1, presence_penalty=-0.5,
                             min_tokens=4, stop_token_ids=(7, 9))
-    assert eng.tok_table.shape == (4, 64) and eng.proc_logits_v.shape == (16, 64)
-    assert eng.samp_minp.tolist() == pytest.approx([0, 0, 0.05, 0]) and eng.v_samp_minp[8:12].tolist() == pytest.approx([0.05] * 4)
-    assert eng.lp_rep.tolist() == [1, 1, float(np.float16(1.2)), 1] and eng.lp_freq[2] == np.float16(0.1) and eng.lp_pres[2] == -0.5
-    assert eng.lp_min_tokens.tolist() == [0, 0, 4, 0] and eng.lp_n_stop.tolist() == [0, 0, 2, 0]
-    assert eng.lp_stop_ids[2, :2].tolist() == [7, 9] and eng.lp_need.tolist() == [0, 0, 1, 0]
-    assert not eng._processing_on()                               # the slot is not occupied yet
+    assert s.tok_table.shape == (4, 64) and s.proc_logits_v.shape == (16, 64)
+    assert s.samp_minp.tolist() == pytest.approx([0, 0, 0.05, 0]) and s.v_samp_minp[8:12].tolist() == pytest.approx([0.05] * 4)
+    assert s.lp_rep.tolist() == [1, 1, float(np.float16(1.2)), 1] and s.lp_freq[2] == np.float16(0.1) and s.lp_pres[2] == -0.5
+    assert s.lp_min_tokens.tolist() == [0, 0, 4, 0] and s.lp_n_stop.tolist() == [0, 0, 2, 0]
+    assert s.lp_stop_ids[2, :2].tolist() == [7, 9] and s.lp_need.tolist() == [0, 0, 1, 0]
+    assert not s.processing_on(eng.active_slots())   # the slot is not occupied yet
     eng._len_ub[2] = 10
-    assert eng._processing_on()
+    assert s.processing_on(eng.active_slots())
     eng.set_sampling_params(3, 0.0, min_p=0.3, min_tokens=2, stop_token_ids=(1,))     # greedy: min_p is reset, the rest stays
-    assert float(eng.samp_minp[3]) == 0.0 and int(eng.lp_min_tokens[3]) == 2 and int(eng.lp_need[3]) == 0
+    assert float(s.samp_minp[3]) == 0.0 and int(s.lp_min_tokens[3]) == 2 and int(s.lp_need[3]) == 0
     eng.set_sampling_params(0, 1.0, min_tokens=5)                 # min_tokens without stop ids masks nothing: neutral
-    assert eng._lp_host[0] == eng._LP_NEUTRAL
+    assert s._lp_host[0] == s._LP_NEUTRAL
     eng.free_slot(2)
-    assert eng._lp_host[2] == eng._LP_NEUTRAL and eng.lp_need.tolist() == [0, 0, 0, 0] and float(eng.samp_minp[2]) == 0.0
-    assert float(eng.lp_rep[2]) == 1.0 and int(eng.lp_n_stop[2]) == 0 and not eng._processing_on()
+    assert s._lp_host[2] == s._LP_NEUTRAL and s.lp_need.tolist() == [0, 0, 0, 0] and float(s.samp_minp[2]) == 0.0
+    assert float(s.lp_rep[2]) == 1.0 and int(s.lp_n_stop[2]) == 0 and not s.processing_on(eng.active_slots())
 
 
 def test_engine_refuses_bad_values_and_enqueues_nothing():
-    eng = _HostEngine()
+    eng = HostEngine()
+    s = eng.sampling
     for kw in (dict(stop_token_ids=tuple(range(17)), min_tokens=1), dict(min_p=1.5), dict(min_p=-0.1),
                dict(repetition_penalty=0.0), dict(repetition_penalty=-1.0), dict(min_tokens=-1), dict(presence_penalty=float("nan")),
                dict(frequency_penalty=1e9)):
         with pytest.raises(ValueError):
             eng.set_sampling_params(1, 0.8, **kw)
-        assert eng._lp_host is None or eng._lp_host[1] == eng._LP_NEUTRAL
-        assert eng._samp_host[1] == (0.0, -1, 1.0)                # refused before anything was uploaded
+        assert s._lp_host is None or s._lp_host[1] == s._LP_NEUTRAL
+        assert s._samp_host[1] == (0.0, -1, 1.0)   # refused before anything was uploaded
     eng._len_ub[1] = 5                                            # an occupied slot has no table row to count in
     with pytest.raises(ValueError, match="admitted"):
         eng.set_sampling_params(1, 0.8, repetition_penalty=1.1)

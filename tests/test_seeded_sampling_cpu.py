@@ -7,7 +7,7 @@ import torch
 
 from qspec_amd import _lib
 from qspec_amd.model import QuarotLlamaConfig
-from qspec_amd.spec_decode.engine import QSpecEngine
+from host_engine import HostEngine
 from test_worker_cpu import FakeEngine, fake_memory_probe
 
 from qspec_amd.spec_decode.worker import (ExecuteModelRequest, SamplingParams, SequenceData, SequenceGroupMetadata,
@@ -64,36 +64,19 @@ def test_unseeded_admission_works_with_an_engine_that_has_no_seed_keyword():
     assert w.engine.sampling[0] == (0.8, -1, 1.0)
 
 
-class _HostEngine(QSpecEngine):
-    """QSpecEngine's slot bookkeeping on host tensors (no model, no GPU)."""
-
-    def __init__(self, B=4, k=3):
-        self.k, self.B, self.device = k, B, torch.device("cpu")
-        self.blocks_per_seq, self.block_size, self.num_blocks = 16, 16, B * 16
-        T = B * (k + 1)
-        self.seq_lens = torch.zeros(B, dtype=torch.int32)
-        self.gen_lens = torch.zeros(B, dtype=torch.int32)
-        self._len_ub, self._gen_ub, self._bt_host = [0] * B, [0] * B, [None] * B
-        self.samp_temp, self.samp_topk, self.samp_topp = torch.zeros(B), torch.full((B,), -1, dtype=torch.int32), torch.ones(B)
-        self.v_samp_temp, self.v_samp_topk, self.v_samp_topp = torch.zeros(T), torch.full((T,), -1, dtype=torch.int32), torch.ones(T)
-        self._samp_host = [(0.0, -1, 1.0)] * B
-        self.seq_seed = torch.zeros(B, dtype=torch.int64)
-        self.seq_seeded = torch.zeros(B, dtype=torch.int32)
-        self._seed_host = [None] * B
-
-
 def test_engine_seed_arrays_follow_set_sampling_params_and_free_slot():
-    eng = _HostEngine()
+    eng = HostEngine()
+    s = eng.sampling
     eng.set_sampling_params(2, 0.8, 50, 0.9, seed=1234)
-    assert eng.seq_seed.tolist() == [0, 0, 1234, 0] and eng.seq_seeded.tolist() == [0, 0, 1, 0]
+    assert s.seq_seed.tolist() == [0, 0, 1234, 0] and s.seq_seeded.tolist() == [0, 0, 1, 0]
     eng.set_sampling_params(1, 1.0, seed=2 ** 64 - 1)          # mod 2^64, stored as the int64 with the same bits
-    assert int(eng.seq_seed[1]) == -1 and int(eng.seq_seeded[1]) == 1
+    assert int(s.seq_seed[1]) == -1 and int(s.seq_seeded[1]) == 1
     eng.set_sampling_params(3, 0.0, seed=5)                     # greedy: no draws, no seed
-    assert int(eng.seq_seeded[3]) == 0
+    assert int(s.seq_seeded[3]) == 0
     eng.set_sampling_params(2, 0.8, 50, 0.9)                    # the seed goes, the parameters stay
-    assert int(eng.seq_seeded[2]) == 0 and eng._samp_host[2] == (0.8, 50, 0.9)
+    assert int(s.seq_seeded[2]) == 0 and s._samp_host[2] == (0.8, 50, 0.9)
     eng.free_slot(1)
-    assert eng.seq_seeded.tolist() == [0, 0, 0, 0] and eng._seed_host == [None] * 4
+    assert s.seq_seeded.tolist() == [0, 0, 0, 0] and s._seed_host == [None] * 4
 
 
 def test_seeded_symbols_declared_bound_and_exported():

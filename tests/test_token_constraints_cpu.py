@@ -17,7 +17,7 @@ import logit_cases as lc  # noqa: E402
 
 from qspec_amd import _lib  # noqa: E402
 from qspec_amd.spec_decode import worker as W  # noqa: E402
-from qspec_amd.spec_decode.engine import QSpecEngine  # noqa: E402
+from host_engine import HostEngine  # noqa: E402
 
 NEW = ("qspec_process_logits_constrained", "qspec_token_constraints_set")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "token_constraints.npz")
@@ -119,25 +119,6 @@ def test_new_symbols_declared_bound_exported_and_validating():
         assert ts(**kw) != 0 and word in lib.qspec_last_error(), (kw, lib.qspec_last_error())
 
 
-class _HostEngine(QSpecEngine):
-    """QSpecEngine's slot bookkeeping on host tensors (no model, no GPU); the admission kernel is recorded, not launched."""
-
-    def __init__(self, B=4, k=3, V=64):
-        self.k, self.B, self.device = k, B, torch.device("cpu")
-        self.cfg = SimpleNamespace(vocab_size=V)
-        self.blocks_per_seq, self.block_size, self.num_blocks = 16, 16, B * 16
-        T = B * (k + 1)
-        self.seq_lens = torch.zeros(B, dtype=torch.int32)
-        self.gen_lens = torch.zeros(B, dtype=torch.int32)
-        self._len_ub, self._gen_ub, self._bt_host = [0] * B, [0] * B, [None] * B
-        self.samp_temp, self.samp_topk, self.samp_topp = torch.zeros(B), torch.full((B,), -1, dtype=torch.int32), torch.ones(B)
-        self.v_samp_temp, self.v_samp_topk, self.v_samp_topp = torch.zeros(T), torch.full((T,), -1, dtype=torch.int32), torch.ones(T)
-        self._samp_host = [(0.0, -1, 1.0)] * B
-        self.seq_seed = torch.zeros(B, dtype=torch.int64)
-        self.seq_seeded = torch.zeros(B, dtype=torch.int32)
-        self._seed_host = [None] * B
-
-
 @pytest.fixture
 def recorded(monkeypatch):
     from qspec_amd import ops
@@ -147,29 +128,31 @@ def recorded(monkeypatch):
 
 
 def test_engine_constraints_follow_set_sampling_params_and_free_slot(recorded):
-    eng = _HostEngine()
+    eng = HostEngine()
+    s = eng.sampling
     eng.set_sampling_params(1, 0.8, 50, 0.9, min_p=0.1)
-    assert eng._tc_host is None and eng.tc is None and not eng._constraints_on()   # nothing asked for: nothing allocated
+    assert s._tc_host is None and s.tc is None and not s.constraints_on(eng.active_slots())   # nothing asked for: nothing allocated
     eng.set_sampling_params(2, 0.0, logit_bias={"7": 1.5, 3: -100.0}, allowed_token_ids=[9, 3, 3, 7],
                             bad_words_token_ids=[[5], [4, 9], [4, 9], [5]])
-    assert eng.tc is not None and eng.tc.deny.shape == (4, 2) and eng.tc.meta.shape == (4, 4) and eng.tok_table is not None
-    assert eng.tc.bias_ids.shape == (4, 512) and eng.tc.words.shape == (4, 32, 8) and eng.tc.tail.shape == (4, 7)
+    assert s.tc is not None and s.tc.deny.shape == (4, 2) and s.tc.meta.shape == (4, 4) and s.tok_table is not None
+    assert s.tc.bias_ids.shape == (4, 512) and s.tc.words.shape == (4, 32, 8) and s.tc.tail.shape == (4, 7)
     assert recorded == [(2, {3: -100.0, 7: 1.5}, (3, 7, 9), [[5], [4, 9]])]
-    assert not eng._constraints_on() and not eng._processing_on()                  # the slot is not occupied yet
+    assert not s.constraints_on(eng.active_slots()) and not s.processing_on(eng.active_slots())   # the slot is not occupied yet
     eng._len_ub[2] = 10
-    assert eng._constraints_on() and eng._processing_on() and not eng._sampling_on()
+    assert s.constraints_on(eng.active_slots()) and s.processing_on(eng.active_slots()) and not s.sampling_on(eng.active_slots())
     eng.set_sampling_params(2, 0.0, logit_bias={3: -100.0, 7: 1.5}, allowed_token_ids=(9, 7, 3), bad_words_token_ids=[(5,), (4, 9)])
     assert len(recorded) == 1                                                      # the same constraints: nothing uploaded
     with pytest.raises(ValueError, match="admitted"):
         eng.set_sampling_params(2, 0.0, logit_bias={3: 1.0})
     eng.free_slot(2)
-    assert recorded[-1] == (2,) and eng._tc_host[2] is None and not eng._constraints_on() and not eng._processing_on()
+    assert recorded[-1] == (2,) and s._tc_host[2] is None and not s.constraints_on(eng.active_slots()) and not s.processing_on(eng.active_slots())
 
 
 def test_engine_refuses_bad_constraints_and_enqueues_nothing(recorded):
-    eng = _HostEngine()
+    eng = HostEngine()
+    s = eng.sampling
     many = {t: 1.0 for t in range(513)}
-    big = _HostEngine(V=1024)
+    big = HostEngine(V=1024)
     for e, kw in ((eng, dict(logit_bias={64: 1.0})), (eng, dict(logit_bias={-1: 1.0})), (eng, dict(logit_bias={"x": 1.0})),
                   (eng, dict(logit_bias={1: float("nan")})), (eng, dict(logit_bias={1: float("inf")})),
                   (eng, dict(allowed_token_ids=[])), (eng, dict(allowed_token_ids=[64])), (eng, dict(bad_words_token_ids=[[]])),
@@ -179,7 +162,7 @@ def test_engine_refuses_bad_constraints_and_enqueues_nothing(recorded):
                   (eng, dict(allowed_token_ids=[3, 4, 5], bad_words_token_ids=[[3]], min_tokens=2, stop_token_ids=(4, 5)))):
         with pytest.raises(ValueError):
             e.set_sampling_params(1, 0.8, **kw)
-        assert e._tc_host is None and e.tc is None and e._samp_host[1] == (0.0, -1, 1.0) and recorded == []
+        assert e.sampling._tc_host is None and e.sampling.tc is None and e.sampling._samp_host[1] == (0.0, -1, 1.0) and recorded == []
     # the same allowed set is fine once min_tokens leaves a token, and 32 words of 8 tokens / 512 biases are inside the caps
     eng.set_sampling_params(1, 0.8, allowed_token_ids=[3, 4, 5, 6], bad_words_token_ids=[[3]], min_tokens=2, stop_token_ids=(4, 5))
     big.set_sampling_params(1, 0.0, logit_bias={t: 1.0 for t in range(512)},
