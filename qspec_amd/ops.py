@@ -7,7 +7,9 @@ and never synchronises.  PyTorch is used for memory and streams only.
 """
 from __future__ import annotations
 
+import contextlib
 import os
+import threading
 from typing import Optional
 
 import torch
@@ -21,12 +23,75 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-def _ws_key(device):
-    """Key of the process-wide scratch / hand-off workspaces: they carry ticket, flag or generation state and are
-    safe for ONE stream at a time (launches on a stream are serialised), so each (device, stream) gets its own."""
+def _device_index(device) -> int:
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
+def _stream_id(device) -> int:
+    """The current stream of `device`: the ONE place the workspace registry learns which stream it is on."""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+# kind -> (library function giving the size in bytes, sized by rows, zero-filled (else merely allocated), dtype)
+_WS_KINDS = {
+    "xwg":     ("qspec_xwg_workspace_bytes", False, True, _I32),              # spread-Hadamard exchange
+    "ln":      ("qspec_ln_linear_workspace_bytes", False, True, _U8),         # norm hand-off of the LN-prologue GEMMs
+    "w4a16":   ("qspec_w4a16_workspace_bytes", False, True, _U8),             # split-K scratch of the W4A16 kernels
+    "sampler": ("qspec_sampler_workspace_bytes", True, False, _U8),           # chunked softmax / rejection partials
+    "lm_head": ("qspec_lm_head_sampler_workspace_bytes", True, False, _U8),   # row maxima of lm_head_softmax_argmax
+    "sample":  ("qspec_sample_workspace_bytes", True, True, _U8),             # histogram of sample_top_k_top_p
+}
+# int32 index of the sticky error word of the kinds that carry one; mirrors QS_XWG_ERR_WORD (csrc/hadamard.hip) and
+# the hand-off kernel's `sync[31]` (csrc/gemm_stream.hip; "int32 word 31" in include/qspec_hip.h)
+_ERROR_WORD = {"xwg": 0, "ln": 31}
+_workspaces = {}    # (kind, device.type, device.index, stream[, rows]) -> tensor
+_tls = threading.local()    # .no_handoffs: how many no_handoffs() blocks this thread is inside
+
+
+def _workspace(kind: str, device, *, rows=None):
+    """The process-wide scratch / hand-off workspace of `kind`.  Workspaces carry ticket, flag or generation state and are
+    safe for ONE stream at a time (launches on a stream are serialised), so each (device, stream[, rows]) gets its own.
+    Created lazily at the first use of its key -- also when that use falls inside a graph capture, where the zero fill
+    becomes a memset node of the graph.  Creating them ahead of capture (on sample_workspace) changes
+    the captured cycle and is left to a change of its own; this is the one place it has to be made."""
+    size_fn, by_rows, zeroed, dtype = _WS_KINDS[kind]
+    assert (rows is not None) == by_rows, kind
     device = torch.device(device)
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    return (device.type, idx, torch.cuda.current_stream(device).cuda_stream)
+    rows = (rows,) if by_rows else ()
+    key = (kind, device.type, _device_index(device), _stream_id(device)) + rows
+    ws = _workspaces.get(key)
+    if ws is None:
+        nbytes = int(getattr(_lib.load(), size_fn)(*rows))
+        ws = _workspaces[key] = (torch.zeros if zeroed else torch.empty)(nbytes // dtype.itemsize, dtype=dtype, device=device)
+    return ws
+
+
+def error_words(device, current_stream_only: bool = False, kind=None):
+    """One-element int32 views of the sticky error words of the device's hand-off workspaces: those of EVERY stream (a
+    captured graph keeps the workspaces of its capture stream), or of the current stream only; `kind`: of that kind only."""
+    device = torch.device(device)
+    want = (device.type, _device_index(device)) + ((_stream_id(device),) if current_stream_only else ())
+    # (list(): a snapshot -- ranks run as threads of one process create workspaces of their own devices meanwhile)
+    return [ws.view(_I32).narrow(0, _ERROR_WORD[key[0]], 1) for key, ws in list(_workspaces.items())
+            if key[0] in _ERROR_WORD and kind in (None, key[0]) and key[1:1 + len(want)] == want]
+
+
+def clear_error_words(device) -> None:
+    for w in error_words(device):
+        w.zero_()
+
+
+@contextlib.contextmanager
+def no_handoffs():
+    """On the calling thread only: xwg_workspace() and ln_linear_workspace() return None, so the kernels that wait for
+    partner workgroups take their one-workgroup / recompute forms (bit-identical).  XWG_SPREAD / LN_HANDOFF, the process
+    defaults, are not touched: other engines of the process (ranks run as threads) keep their launch forms.  Nests."""
+    depth = getattr(_tls, "no_handoffs", 0)
+    _tls.no_handoffs = depth + 1
+    try:
+        yield
+    finally:
+        _tls.no_handoffs = depth
 
 
 def _chk(t: torch.Tensor, name: str, dtype=None):
@@ -245,28 +310,20 @@ def silu_mul_hadamard(gate_up, hadK, K: int, had_scale: float, out_f16=None, q=N
           float(clip_ratio), T, two_i // 2, K, _stream())
 
 
-_xwg_ws = {}
 XWG_SPREAD = os.environ.get("QSPEC_XWG_SPREAD", "1") != "0"   # False: one workgroup per token (no workspace)
 
 
 def xwg_workspace(device):
     """Exchange workspace of the kernels that spread one token over several workgroups (mlp_hadamard,
-    heads_hadamard_merged): zero-filled once, never reset; one per (device, stream) -- launches on one stream are
-    serialised, two streams must not share its counters.  Word 0 is a sticky error flag (xwg_error)."""
-    if not XWG_SPREAD:
+    heads_hadamard_merged): zero-filled once, never reset.  None: the one-workgroup forms.  Sticky error flag: _ERROR_WORD."""
+    if not XWG_SPREAD or getattr(_tls, "no_handoffs", 0):
         return None
-    key = _ws_key(device)
-    if key not in _xwg_ws:
-        _xwg_ws[key] = torch.zeros(int(_lib.load().qspec_xwg_workspace_bytes()) // 4, dtype=torch.int32, device=device)
-    return _xwg_ws[key]
+    return _workspace("xwg", device)
 
 
 def xwg_error_word(device):
-    """Sticky error flags of EVERY exchange workspace of the device (a captured graph keeps the workspace of its
-    capture stream): an int32 tensor [n] (one word per workspace), or None if none exists."""
-    device = torch.device(device)
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    words = [ws[:1] for key, ws in _xwg_ws.items() if key[:2] == (device.type, idx)]
+    """Sticky error flags of EVERY exchange workspace of the device: int32 [n] (one word per workspace), or None if none."""
+    words = error_words(device, kind="xwg")
     return torch.cat(words) if words else None
 
 
@@ -347,7 +404,6 @@ def ln_linear_s4s4_supported(M: int, N: int, K: int) -> bool:
     return bool(_lib.load().qspec_ln_linear_s4s4_supported(M, N, K))
 
 
-_ln_ws = {}
 LN_HANDOFF_MIN_M = int(os.environ.get("QSPEC_LN_HANDOFF_MIN_M", "8"))
 LN_HANDOFF = os.environ.get("QSPEC_LN_HANDOFF", "1") != "0"   # False: every workgroup recomputes the norm (no workspace)
 
@@ -356,20 +412,9 @@ def ln_linear_workspace(device, M: int = 16):
     """Hand-off workspace of the LN-prologue GEMMs (zero-filled once; every call leaves it zeroed).  Measured on
     MI355X: up to 4 tokens every workgroup recomputing the norm is faster (10.4 vs 12.2 us for qkv_proj), from 8
     tokens the producer / hand-off form wins (15 vs 25 us at 16 tokens)."""
-    if not LN_HANDOFF or M < LN_HANDOFF_MIN_M:
+    if not LN_HANDOFF or M < LN_HANDOFF_MIN_M or getattr(_tls, "no_handoffs", 0):
         return None
-    key = _ws_key(device)
-    if key not in _ln_ws:
-        _ln_ws[key] = torch.zeros(int(_lib.load().qspec_ln_linear_workspace_bytes()), dtype=torch.uint8, device=device)
-    return _ln_ws[key]
-
-
-def ln_linear_error_word(device):
-    """Sticky error words of every norm hand-off workspace of the device (int32 [n]) or None."""
-    device = torch.device(device)
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    words = [ws.view(torch.int32)[31:32] for key, ws in _ln_ws.items() if key[:2] == (device.type, idx)]
-    return torch.cat(words) if words else None
+    return _workspace("ln", device)
 
 
 def ln_qkv_rope_linear(hidden_in, delta, hidden_out, eps, wq, w_scale, qkv, positions, cos_sin_cache, key_cache,
@@ -443,16 +488,10 @@ def rowwise_scaled_linear_s4s4_residual_hq_supported(M: int, N: int, K: int, n_p
     return bool(_lib.load().qspec_rowwise_scaled_linear_s4s4_residual_hq_supported(M, N, K, n_parts))
 
 
-_w16_ws = {}
-
-
 def w4a16_workspace(device):
     """Zero-initialised split-K scratch of the W4A16 kernels, one per (device, stream): calls on one stream are
     serialised, so they can share it (every call leaves the ticket counters at zero); two streams must not."""
-    key = _ws_key(device)
-    if key not in _w16_ws:
-        _w16_ws[key] = torch.zeros(int(_lib.load().qspec_w4a16_workspace_bytes()), dtype=torch.uint8, device=device)
-    return _w16_ws[key]
+    return _workspace("w4a16", device)
 
 
 def w4a16_linear(x, wq, w_scale, out, bias=None, xp: bool = False, tokens=None):
@@ -663,18 +702,9 @@ def embedding(ids, table, out):
     return out
 
 
-_ws_cache = {}
-
-
 def _sampler_ws(rows: int, device, workspace=None):
     """Scratch for the chunked softmax / rejection kernels (64 partials per row); cached per (device, stream, rows)."""
-    if workspace is not None:
-        return workspace
-    key = (_ws_key(device), rows)
-    if key not in _ws_cache:
-        n = int(_lib.load().qspec_sampler_workspace_bytes(rows))
-        _ws_cache[key] = torch.empty(n, dtype=torch.uint8, device=device)
-    return _ws_cache[key]
+    return workspace if workspace is not None else _workspace("sampler", device, rows=rows)
 
 
 def softmax_argmax(logits, probs, token, workspace=None):
@@ -682,9 +712,6 @@ def softmax_argmax(logits, probs, token, workspace=None):
     ws = _sampler_ws(T, logits.device, workspace)
     _call("qspec_softmax_argmax", _chk(logits, "logits", _F16), _chk(probs, "probs", _F32), _chk(token, "token", _I64),
           T, V, ws.data_ptr(), _stream())
-
-
-_head_ws = {}
 
 
 def lm_head_softmax_argmax_supported(T: int, V: int, K: int) -> bool:
@@ -696,13 +723,9 @@ def lm_head_softmax_argmax(hidden, lm_head, logits, probs, token):
     hands its row maxima to the softmax, probs is written once (logits_processor.py:92-97 + sampler.py:270-287)."""
     T, K = hidden.shape
     V = lm_head.shape[0]
-    key = (_ws_key(hidden.device), T)
-    if key not in _head_ws:
-        _head_ws[key] = torch.empty(int(_lib.load().qspec_lm_head_sampler_workspace_bytes(T)), dtype=torch.uint8,
-                                    device=hidden.device)
     _call("qspec_lm_head_softmax_argmax", _chk(hidden, "hidden", _F16), _chk(lm_head, "lm_head", _F16),
           _chk(logits, "logits", _F16), _chk(probs, "probs", _F32), _chk(token, "token", _I64), T, V, K,
-          _head_ws[key].data_ptr(), _stream())
+          _workspace("lm_head", hidden.device, rows=T).data_ptr(), _stream())
 
 
 def _seq_seed_args(seq_seeds, seq_seeded, base_pos, nseq: int):
@@ -744,15 +767,9 @@ def rejection_sample(target_with_bonus_probs, bonus_token_ids, draft_probs, draf
         _call("qspec_rejection_sample_seeded", *args, *seeded, ws, _stream())
 
 
-_sample_ws = {}
-
-
 def sample_workspace(rows: int, device):
     """Histogram workspace of sample_top_k_top_p: zero-filled once per (device, stream, rows), left zeroed by every call."""
-    key = _ws_key(device) + (rows,)
-    if key not in _sample_ws:
-        _sample_ws[key] = torch.zeros(int(_lib.load().qspec_sample_workspace_bytes(rows)), dtype=torch.uint8, device=device)
-    return _sample_ws[key]
+    return _workspace("sample", device, rows=rows)
 
 
 def new_sample_workspace(rows: int, device):
@@ -1062,16 +1079,8 @@ def spec_snapshot(seq_lens, gen_lens, last_token, counters, rng_state, snap_i32,
 
 def stream_error_words(device, extra=()):
     """Raw device addresses of the sticky error words of the CURRENT stream's hand-off workspaces (the ones the launches
-    being enqueued on this stream use; a captured graph keeps those of its capture stream) plus `extra` addresses (the
-    one-shot all-reduce's word)."""
-    key = _ws_key(device)
-    ptrs = []
-    if key in _xwg_ws:
-        ptrs.append(_xwg_ws[key][:1].data_ptr())
-    if key in _ln_ws:
-        ptrs.append(_ln_ws[key].view(torch.int32)[31:32].data_ptr())
-    ptrs += [int(p) for p in extra if p]
-    return ptrs
+    being enqueued on this stream use) plus `extra` addresses (the one-shot all-reduce's word)."""
+    return [w.data_ptr() for w in error_words(device, current_stream_only=True)] + [int(p) for p in extra if p]
 
 
 def collect_error_words(word_addrs, out=None, clear: bool = False):

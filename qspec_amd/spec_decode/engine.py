@@ -693,23 +693,12 @@ class QSpecEngine:
         ops.spec_snapshot(self.seq_lens, self.gen_lens, self.last_token, self.sampler.counters, self.sampler.rng_state,
                           self._snap_i32, self._snap_i64, restore=True)
         self.clear_error_words()
-        saved = ops.XWG_SPREAD, ops.LN_HANDOFF
-        ops.XWG_SPREAD = ops.LN_HANDOFF = False
-        try:
+        with ops.no_handoffs():   # this thread only: other engines of the process keep their launch forms
             self._cycle_body()
-        finally:
-            ops.XWG_SPREAD, ops.LN_HANDOFF = saved
         self.recoveries += 1
 
     def clear_error_words(self) -> None:
-        dev = self.device
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        for key, ws in ops._xwg_ws.items():
-            if key[:2] == (dev.type, idx):
-                ws[:1].zero_()
-        for key, ws in ops._ln_ws.items():
-            if key[:2] == (dev.type, idx):
-                ws.view(torch.int32)[31:32].zero_()
+        ops.clear_error_words(self.device)
         tp = self._comm()
         if tp is not None and hasattr(tp.comm, "error_word_address"):
             ops.collect_error_words([tp.comm.error_word_address()], clear=True)
@@ -718,7 +707,7 @@ class QSpecEngine:
     def error_flag(self) -> int:
         """Sticky device-side error words of EVERY hand-off workspace of the device and of the one-shot all-reduce, read
         from the host (0 = fine).  The cycle itself reports through read_outputs(); this is the out-of-band check."""
-        words = [w for w in (ops.xwg_error_word(self.device), ops.ln_linear_error_word(self.device)) if w is not None]
+        words = ops.error_words(self.device)
         flag = int(torch.cat(words).abs().max().item()) if words else 0
         tp = self._comm()
         if tp is not None and hasattr(tp.comm, "error"):

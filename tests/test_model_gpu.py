@@ -1294,6 +1294,61 @@ def test_cycle_recovery_replay_is_bit_identical(tiny, width, B):
     assert runs[0][2:] == runs[1][2:]
 
 
+def test_recovery_replay_launches_without_handoff_workspaces(monkeypatch):
+    """engine.recover() replays the cycle inside ops.no_handoffs(): every MLP-Hadamard launch and every fused-norm GEMM
+    of the replay gets a NULL workspace while ops.XWG_SPREAD / ops.LN_HANDOFF -- the defaults of every other engine of the
+    process -- stay as they were, and the step after it passes the workspaces again.  LN_HANDOFF_MIN_M is lowered to 1:
+    at its default of 8 the 4 draft rows would get a NULL sync workspace with or without a recovery."""
+    from qspec_amd import ops
+    from qspec_amd.model import QuarotLlamaConfig, QuarotLlamaForCausalLM
+    from qspec_amd.spec_decode import QSpecEngine
+    monkeypatch.setattr(ops, "LN_HANDOFF_MIN_M", 1)
+    B = 4
+    cfg = QuarotLlamaConfig(4096, 14336, 32, 8, 2, 1024, 1e-5, 500000.0, 512, "llama-3-8b-2layer")
+    model = QuarotLlamaForCausalLM(cfg, DEV).init_synthetic(seed=4, lm_head_std=0.05)
+    assert B <= model.FUSE_LN_MAX_M
+    rng = np.random.default_rng(16)
+    eng = QSpecEngine(model, 3, B, max_model_len=256, block_size=16, max_new_tokens=64, use_graph=False, seed=11)
+    eng.add_sequences([rng.integers(0, cfg.vocab_size, n).tolist() for n in (20, 31, 8, 50)])
+    defaults = ops.XWG_SPREAD, ops.LN_HANDOFF
+    assert defaults == (True, True)
+    call, seen = ops._call, []
+
+    def recorder(name, *args):
+        if name.startswith("qspec_mlp_hadamard") or (name.startswith("qspec_ln_") and "_s4s4" in name):
+            seen.append((name, args[-2], (ops.XWG_SPREAD, ops.LN_HANDOFF)))   # (.., workspace, stream)
+        call(name, *args)
+
+    def families(null):
+        had = [ws for name, ws, _ in seen if name.startswith("qspec_mlp_hadamard")]
+        ln = [ws for name, ws, _ in seen if name.startswith("qspec_ln_")]
+        assert had and ln, "the replay took neither hand-off family: nothing was checked"
+        assert all((ws is None) == null for ws in had + ln), seen
+        assert all(switches == defaults for _, _, switches in seen)
+    eng.step()
+    out, err = eng.read_outputs()
+    assert err == 0
+    eng.note_emitted([int((out[b] != -1).sum()) for b in range(B)])
+    ops.xwg_workspace(DEV)[:1].fill_(1)   # raise this stream's sticky exchange-workspace error word
+    eng.step()
+    out, err = eng.read_outputs()
+    assert err != 0
+    with monkeypatch.context() as m:
+        m.setattr(ops, "_call", recorder)
+        eng.recover()
+    families(null=True)
+    assert (ops.XWG_SPREAD, ops.LN_HANDOFF) == defaults
+    out, err = eng.read_outputs()
+    assert err == 0 and eng.recoveries == 1 and eng.error_flag() == 0
+    eng.note_emitted([int((out[b] != -1).sum()) for b in range(B)])
+    del seen[:]
+    with monkeypatch.context() as m:
+        m.setattr(ops, "_call", recorder)
+        eng.step()
+    families(null=False)
+    assert eng.read_outputs()[1] == 0 and eng.error_flag() == 0
+
+
 def test_fallback_mode_reports_and_recovers_errors(tiny):
     """The draft-graph + eager-verify fallback (taken when the cycle's collectives cannot be captured) carries the same
     bracket as the captured cycle: the state snapshot at the head of the draft graph, the error words collected behind the
