@@ -12,8 +12,10 @@ Two implementations of the layer body:
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
-from typing import List, Optional
+import os
+from dataclasses import dataclass
+from types import SimpleNamespace
+from typing import List, NamedTuple, Optional
 
 import torch
 
@@ -101,14 +103,10 @@ class Scratch:
         # verify pass: raw fp32 K-slice sums of down_proj, finished inside the next norm (ops.w4a16_linear_partial)
         # (17..256 tokens: the M-tiled kernel's plan slices narrow layers up to eight ways)
         self.down_part = e(4 if T <= 16 else 8, T, H, dtype=torch.float32) if T <= 256 else None
-        # verify pass at <= 16 tokens: fragment-major 16-row activation tiles between the producers and the W4A16 GEMMs
-        # (ops.w4a16_act_layout_supported); rows past T are never read back into a result
-        z = lambda k: torch.zeros(16, k, dtype=f16, device=device)  # noqa: E731
-        self.xp_normed, self.xp_had, self.xp_had_mlp = (z(H), z(cfg.q_size), z(I)) if T <= 16 else (None, None, None)
-        if 16 < T <= 32:   # two tiles each: the two-token-tile W4A16 streaming kernel (ops.w4a16_act_layout32_supported)
-            self.xp_normed = torch.zeros(32, H, dtype=f16, device=device)
-            self.xp_had = torch.zeros(32, cfg.q_size, dtype=f16, device=device)
-            self.xp_had_mlp = torch.zeros(32, I, dtype=f16, device=device)
+        # verify pass: fragment-major 16-row activation tiles between the producers and the W4A16 GEMMs -- one up to 16 tokens
+        # (ops.w4a16_act_layout_supported), two up to 32 (..._layout32_supported); rows past T are never read back into a result
+        z = lambda k: torch.zeros(16 if T <= 16 else 32, k, dtype=f16, device=device) if T <= 32 else None  # noqa: E731
+        self.xp_normed, self.xp_had, self.xp_had_mlp = z(H), z(cfg.q_size), z(I)
         self.tp_part = e(1, min(T, 32), H, dtype=torch.float32)   # TP verify pass (T <= 32): fp32 row-parallel partials
         self.had_part_amax = e(min(T, 16), 8, dtype=torch.float32)  # draft pass (T <= 4): partial row maxima of the spread head Hadamard
         # draft pass at 17..32 tokens: int32 K-slice sums of down_proj + the activation scales they were computed with
@@ -116,6 +114,52 @@ class Scratch:
         self.down_xs = e(T) if 16 < T <= 32 else None
         ws = ops.paged_attention_workspace_bytes(n_seqs * max_q_len, cfg.num_attention_heads, cfg.head_dim, n_splits)
         self.attn_ws = torch.zeros(ws, dtype=torch.uint8, device=device)   # ticket counters start at zero
+
+    def k_slices(self, S: int, T: int, int32: bool = False):
+        """[S, T, H] at the head of down_part (raw fp32 K-slice sums of a W4A16 GEMM) or down_ipart (int32, of an s4s4 GEMM)."""
+        buf = self.down_ipart if int32 else self.down_part
+        H = buf.shape[-1]
+        return buf.view(-1)[:S * T * H].view(S, T, H)
+
+    def mlp_rows(self, T: int):
+        """[T, I] at the head of act_buffer_gate_up: where the fp16 MLP transform goes once gate_up's output is consumed."""
+        I = self.act_buffer_gate_up.shape[1] // 2
+        return self.act_buffer_gate_up.view(-1)[:T * I].view(T, I)
+
+
+@dataclass(frozen=True)
+class ForwardPlan:
+    """The launch form of one forward() call (QuarotLlamaForCausalLM._plan); the layer stages branch on nothing else."""
+    form: str        # last_forward_form: "two-tile" | "fragment-major" | "fused" | "unfused"
+    w4a4: bool       # draft pass
+    fuse: bool       # fused GEMM epilogues (qkv + RoPE + KV write, gate_up + SiLU)
+    ln_fused: bool   # draft: residual add + LN + int4 quant in the qkv / gate_up prologues (gemm_stream.hip), no hand-over
+    hq: bool         # ... and the head transform's quantiser in o_proj's prologue
+    xp: bool         # verify, <= 16 tokens: fragment-major activation tiles
+    xp32: bool       # verify, 17..32 tokens: two tiles, the two-token-tile streaming kernel
+    tp_on: bool      # verify: o_proj / gate_up / down_proj sharded over self.tp
+    heads: str       # head transform: "merged" | "mix_merged" (it merges the attention's context splits) | "generic"
+    S_down: int      # K slices whose raw sums the next norm finishes (0: the plain launch) of the draft down_proj (int32 sums),
+    S_mlp: int       # ... the verify down_proj,
+    S_o: int         # ... the verify o_proj,
+    S32: int         # ... the down_proj of the two-tile form
+
+
+class Delta(NamedTuple):
+    """What a projection hands to the next norm, which adds it to the residual stream: its fp16 output (f16), its raw K-slice
+    sums -- fp32 of a W4A16 GEMM (part), int32 of an s4s4 GEMM with its activation scales (ipart, x_scale) -- or nothing."""
+    f16: Optional[torch.Tensor] = None
+    part: Optional[torch.Tensor] = None
+    ipart: Optional[torch.Tensor] = None
+    x_scale: Optional[torch.Tensor] = None
+    w_scale: Optional[torch.Tensor] = None
+    slices: int = 0
+
+
+def _knob(name: str, default):
+    """The environment's QSPEC_<name>: an int where the default is one, else a switch that only "0" turns off."""
+    v = os.environ.get("QSPEC_" + name)
+    return default if v is None else (v != "0" if isinstance(default, bool) else int(v))
 
 
 class DecoderLayerWeights:
@@ -175,56 +219,27 @@ class QuarotLlamaForCausalLM:
     # (gemm_tiled.hip) + separate RoPE / SiLU launches is faster than the first-generation 2-D kernel that used to take
     # 17..64 rows (Llama-3-70B, bs = 8, T = 32: 51.2 -> 47.9 ms per cycle; Llama-3-8B bs = 8: 9.81 -> 9.56).  The
     # tensor-parallel shard views (K-sliced / channel-sharded streaming forms, T <= 32) keep the fused path.
-    VERIFY_FUSE_MAX_M = int(__import__("os").environ.get("QSPEC_VERIFY_FUSE_MAX_M", "16"))
+    VERIFY_FUSE_MAX_M = _knob("VERIFY_FUSE_MAX_M", 16)
     # draft pass: LN in the GEMM prologue up to this many tokens (0 = always a separate LN launch; bit-identical).
     # Measured in the engine (round 2): bs = 4 fused 8.39 vs separate 8.43 ms per cycle; bs = 16 fused (hand-off form)
     # 14.30 vs separate 13.38 ms -- the standalone norm launch (3.4 us) beats the hand-off from 8 tokens on.
-    FUSE_LN_MAX_M = int(__import__("os").environ.get("QSPEC_FUSE_LN_MAX_M", "4"))
-    VERIFY_O_SLICES = int(__import__("os").environ.get("QSPEC_VERIFY_O_SLICES", "0"))   # dev knob, see the o_proj branch below
+    FUSE_LN_MAX_M = _knob("FUSE_LN_MAX_M", 4)
+    # dev knob (2 / 4): the verify o_proj at <= 16 tokens as K slices whose raw sums the norm finishes, as down_proj's are --
+    # measured, not the default: the slice order of the sum also breaks the bit identity with the
+    # module-wise path
+    VERIFY_O_SLICES = _knob("VERIFY_O_SLICES", 0)
     FUSE_LN = True
-    # draft pass, T <= 4, 32 heads of 128: head Hadamard spread over 8 workgroups per token + the quantiser in o_proj's prologue
-    HADAMARD_QUANT_IN_OPROJ = __import__("os").environ.get("QSPEC_HQ_OPROJ", "1") != "0"
-
+    # draft pass, T <= 4, 32 heads of 128: merge + head Hadamard spread over 8 workgroups per token (fp16 + partial row maxima),
+    # the Quantizer of :235-238 in the o_proj launch's prologue: same bits as the quantising head transform + plain o_proj
+    HADAMARD_QUANT_IN_OPROJ = _knob("HQ_OPROJ", True)
     # verify pass at <= 16 tokens (one GPU): the norm / head transform / MLP transform store their fp16 rows as the
     # FRAGMENT-MAJOR tile the W4A16 GEMMs' MFMA operands are loaded from (include/qspec_hip.h "activation layout"), which
     # removes the LDS regrouping pass from the head of four launches per layer.  Same bits either way.
-    ACT_FRAGMENT_MAJOR = __import__("os").environ.get("QSPEC_ACT_FRAGMENT_MAJOR", "1") != "0"
-
-    def _w4a16(self, x, lin, out, xp=False, tokens=None):
-        # every M reads the packed int4 buffer: streaming kernel (M <= 16), M-tiled kernel (prefill-sized M)
-        return ops.w4a16_linear(x, lin.weight, lin._scales(), out, xp=xp, tokens=tokens)
-
-    def _add_norm_fp16(self, normed, hidden, delta, eps, xp=False):
-        """hidden += delta; normed = LN(hidden).  delta: fp16 tensor, None, or ("partial", part, w_scale, S) = the raw
-        K-slice sums of a long-K W4A16 down_proj, finished inside the norm kernel.  xp: normed is a fragment-major tile."""
-        if isinstance(delta, tuple) and delta[0] == "ipartial":
-            _, ipart, xs, w_scale, S = delta
-            ops.add_rms_norm_ipartial(hidden, hidden, ipart, xs, w_scale, S, eps, out_f16=normed)
-        elif isinstance(delta, tuple):
-            _, part, w_scale, S = delta
-            ops.add_rms_norm_fp16_partial(normed, hidden, hidden, part, w_scale, S, eps, xp=xp)
-        else:
-            ops.add_rms_norm_fp16(normed, hidden, hidden, delta, eps, xp=xp)
-
-    def _fragment_major_ok(self, T, md, s):
-        """Every producer and consumer of the verify pass has its fragment-major form at this shape."""
-        cfg = self.config
-        H, I, nh, hd = cfg.hidden_size, cfg.intermediate_size, cfg.num_attention_heads, cfg.head_dim
-        if not (self.ACT_FRAGMENT_MAJOR and s.xp_normed is not None and T <= 16 and self.MERGE_IN_HADAMARD
-                and self.VERIFY_O_SLICES <= 1 and hd == 128 and md.n_splits <= 64):
-            return False
-        S = ops.w4a16_linear_partial_slices(T, H, I) if s.down_part is not None else 0
-        down_k = I // S if 0 < S <= 4 else (I if S == 0 else 0)
-        heads_ok = (nh == 32 if self.head_had_K == 1 else
-                    ops.heads_hadamard_mix_merged_spread_supported(T, nh, hd, self.head_had_K))
-        return bool(down_k and heads_ok and ops.w4a16_act_layout_supported(T, H)
-                    and ops.w4a16_act_layout_supported(T, cfg.q_size) and ops.w4a16_act_layout_supported(T, down_k)
-                    and ops.mlp_hadamard_act_layout_supported(T, I, self.had_K))
-
-    XP32_DOWN_SLICES = __import__("os").environ.get("QSPEC_XP32_DOWN_SLICES", "1") != "0"
-    TILED_PARTIAL_IN_NORM = __import__("os").environ.get("QSPEC_TILED_PARTIAL_IN_NORM", "1") != "0"
+    ACT_FRAGMENT_MAJOR = _knob("ACT_FRAGMENT_MAJOR", True)
+    XP32_DOWN_SLICES = _knob("XP32_DOWN_SLICES", True)
+    TILED_PARTIAL_IN_NORM = _knob("TILED_PARTIAL_IN_NORM", True)
     MERGE_IN_HADAMARD = True   # False: the attention kernel merges its context splits itself (ticket + fences)
-    DOWN_K_SLICES = __import__("os").environ.get("QSPEC_DOWN_K_SLICES", "1") != "0"   # draft down_proj at 17..32 tokens as K slices
+    DOWN_K_SLICES = _knob("DOWN_K_SLICES", True)   # draft down_proj at 17..32 tokens as K slices
 
     # FP8 KV cache: per-layer (k_scale, v_scale) read from the checkpoint (model.layers.{i}.self_attn.k_scale / .v_scale);
     # None = 1.0 everywhere.  Only consulted when the cache tensors are bytes.  A caller with scales of its own (the engine's
@@ -242,271 +257,256 @@ class QuarotLlamaForCausalLM:
         ks, vs = kv_scales[li] if kv_scales is not None else (1.0, 1.0)
         return {"k_scale": float(ks), "v_scale": float(vs)}
 
-    def _attention_hadamard(self, qkv, row, kc, vc, md, T, s, attn, q1, sc, had, xp=False, kvs=None):
-        """Attention + head Hadamard (+ quant when q1 is given, else fp16 into `had`) (quarot_llama.py:213-238).
-        For 32 / 64 heads of 128 the split merge of the attention kernel runs at the head of the Hadamard launch."""
-        cfg = self.config
-        nh = cfg.num_attention_heads
-        B = md.ctx_lens.numel()
-        # (other head sizes -- TinyLlama's 64 -- leave their split partials to the same launch when there are 32 heads)
-        merged = (self.MERGE_IN_HADAMARD and md.n_splits <= 64 and self.head_had_K == 1
-                  and ((cfg.head_dim == 128 and nh in (32, 64)) or (cfg.head_dim != 128 and cfg.head_dim % 8 == 0 and nh == 32)))
-        # head count with a table factor (40 heads = had40): the split merge + transform spread over 8 workgroups per token
-        mix_merged = (self.MERGE_IN_HADAMARD and self.head_had_K > 1 and md.n_splits <= 64
-                      and ops.heads_hadamard_mix_merged_spread_supported(T, nh, cfg.head_dim, self.head_had_K))
-        ops.paged_attention(qkv, row, kc, vc, md.block_tables, md.ctx_lens, md.q_start, T, md.max_q_len, nh,
-                            self.sm_scale, md.n_splits, s.attn_ws, None if (merged or mix_merged) else attn, **(kvs or {}))
-        if self.head_had_K > 1:
-            buf = had if had is not None else s.act_buffer_had[:T]
-            if mix_merged:
-                ops.heads_hadamard_mix_merged_spread(s.attn_ws, B * md.max_q_len, md.n_splits, T, nh, cfg.head_dim, self.head_had,
-                                                     self.head_had_K, self.head_had_scale, buf, xp=xp)
-            else:   # generic kernels: one workgroup per token
-                ops.heads_hadamard_mix(attn.view(T, nh, cfg.head_dim), self.head_had, self.head_had_K, self.head_had_scale, buf)
-            if q1 is not None:
-                ops.fuse_sym_quant(buf, sc, q1)
-        elif merged:
-            ops.heads_hadamard_merged(s.attn_ws, B * md.max_q_len, md.n_splits, T, nh, cfg.head_dim,
-                                      self.head_had_scale, out_f16=had, q=q1, scale=sc, xp=xp)
-        elif q1 is not None:
-            ops.heads_hadamard(attn, self.head_had_scale, q=q1, scale=sc, heads=nh)
-        else:
-            ops.heads_hadamard(attn, self.head_had_scale, out_f16=had, heads=nh)
-
     def weight_bytes(self):
         n = sum(lin.weight.numel() + lin.weight_scales.numel() * 2 for l in self.layers for lin in l.linears())
         return n + self.embed_tokens.numel() * 2 + self.lm_head.numel() * 2
 
     # ------------------------------------------------------------------ fused product path
+    def _plan(self, T: int, w4a4: bool, n_splits: int, s: Scratch) -> ForwardPlan:
+        """Every launch-form decision of one forward() call, from host values only: the config, the knobs above, self.tp,
+        which optional buffers `s` has, and the library's shape queries.  Not memoised: the knobs may change between calls."""
+        cfg, K = self.config, self.head_had_K
+        H, I, Q, nh, hd = cfg.hidden_size, cfg.intermediate_size, cfg.q_size, cfg.num_attention_heads, cfg.head_dim
+        row = Q + 2 * cfg.kv_size
+        tp_sharded = self.tp is not None and self.tp.world > 1 and getattr(self.tp, "shard_layers", True) and not w4a4
+        # (head size 64 -- TinyLlama -- has the fused qkv + RoPE + KV-write epilogue on the streaming kernels only)
+        fuse_hd = hd == 128 or (hd == 64 and T <= 32 and ops.qkv_rope_linear_supported(w4a4, T, row, H, 64))
+        fuse = fuse_hd and (w4a4 or T <= (min(self.BIG_M, 32) if tp_sharded else self.VERIFY_FUSE_MAX_M))
+        # tensor parallelism only on the verify pass at decode-sized M; the draft pass and prefill run replicated
+        tp_on = tp_sharded and fuse and T <= 32
+        # head transform: for 32 / 64 heads of 128 the split merge of the attention kernel runs at the head of the Hadamard
+        # launch (other head sizes -- TinyLlama's 64 -- leave their split partials to the same launch when there are 32 heads);
+        # a head count with a table factor (40 heads = had40) spreads merge + transform over 8 workgroups per token
+        splits_ok = self.MERGE_IN_HADAMARD and n_splits <= 64
+        mix_spread = splits_ok and K > 1 and ops.heads_hadamard_mix_merged_spread_supported(T, nh, hd, K)
+        merged = splits_ok and K == 1 and ((hd == 128 and nh in (32, 64)) or (hd != 128 and hd % 8 == 0 and nh == 32))
+        ln_fused = bool(w4a4 and fuse and self.FUSE_LN and T <= self.FUSE_LN_MAX_M
+                        and ops.ln_linear_s4s4_supported(T, row, H) and ops.ln_linear_s4s4_supported(T, 2 * I, H)
+                        and ops.rowwise_scaled_linear_s4s4_residual_supported(T, H, H)
+                        and ops.rowwise_scaled_linear_s4s4_residual_supported(T, H, I))
+        hq = bool(ln_fused and self.HADAMARD_QUANT_IN_OPROJ and splits_ok
+                  and (ops.heads_hadamard_merged_spread_supported(T, nh, hd) if K == 1 else mix_spread)
+                  and ops.rowwise_scaled_linear_s4s4_residual_hq_supported(T, H, Q))
+        S_down = (ops.rowwise_scaled_linear_s4s4_partial_slices(T, H, I)
+                  if (w4a4 and fuse and not ln_fused and s.down_ipart is not None and self.DOWN_K_SLICES) else 0)
+        # verify down_proj as K slices: long K at <= 16 tokens (streaming kernel), narrow layers above (M-tiled kernel's plan)
+        S = (ops.w4a16_linear_partial_slices(T, H, I) if (not w4a4 and not tp_on and s.down_part is not None
+                                                          and (fuse or (T > 16 and self.TILED_PARTIAL_IN_NORM))) else 0)
+        tiles = not w4a4 and not tp_sharded and self.ACT_FRAGMENT_MAJOR and splits_ok and hd == 128 and s.xp_normed is not None
+        # verify pass at <= 16 tokens: every producer and consumer has its fragment-major form at this shape
+        down_k = I // S if 0 < S <= 4 else (I if S == 0 else 0)
+        xp = bool(tiles and fuse and T <= 16 and self.VERIFY_O_SLICES <= 1 and down_k and (nh == 32 if K == 1 else mix_spread)
+                  and ops.w4a16_act_layout_supported(T, H) and ops.w4a16_act_layout_supported(T, Q)
+                  and ops.w4a16_act_layout_supported(T, down_k) and ops.mlp_hadamard_act_layout_supported(T, I, self.had_K))
+        # verify pass at 17..32 tokens: qkv / o_proj / gate_up on the two-token-tile W4A16 streaming kernel over two
+        # fragment-major tiles (fused epilogues as at <= 16 tokens); down_proj stays on the M-tiled kernel (its K passes lose) ...
+        xp32 = bool(tiles and not fuse and 16 < T <= 32 and s.xp_normed.shape[0] == 32
+                    and ops.w4a16_act_layout32_supported(T, row, H) and ops.w4a16_act_layout32_supported(T, H, Q)
+                    and ops.w4a16_act_layout32_supported(T, 2 * I, H) and (nh in (32, 64) if K == 1 else mix_spread))
+        # ... or runs as one-pass K slices of the same kernel across the workgroups, finished inside the next norm
+        S32 = (ops.w4a16_linear_partial_slices_xp32(T, H, I) if (xp32 and s.down_part is not None and self.XP32_DOWN_SLICES
+                                                                 and ops.mlp_hadamard_act_layout_supported(T, I, self.had_K)) else 0)
+        # verify o_proj at 17+ tokens: where the M-tiled kernel's plan slices K, the norm finishes the raw sums (same bits)
+        sliced_o = not (w4a4 or tp_on or xp or xp32) and s.down_part is not None
+        S_o = ops.w4a16_linear_partial_slices(T, H, Q) if (sliced_o and T > 16 and self.TILED_PARTIAL_IN_NORM) else 0
+        S_o = S_o if 1 < S_o <= 8 else 0
+        if sliced_o and fuse and T <= 16 and self.VERIFY_O_SLICES > 1:
+            S_o = self.VERIFY_O_SLICES
+        return ForwardPlan(form="two-tile" if xp32 else ("fragment-major" if xp else ("fused" if fuse else "unfused")),
+                           w4a4=w4a4, fuse=bool(fuse), ln_fused=ln_fused, hq=hq, xp=xp, xp32=xp32, tp_on=bool(tp_on),
+                           heads="mix_merged" if mix_spread else ("merged" if merged else "generic"),
+                           S_down=S_down if S_down > 1 else 0, S_mlp=S if 0 < S <= (4 if T <= 16 else 8) else 0,
+                           S_o=S_o, S32=S32 if 1 < S32 <= 8 else 0)
+
     def forward(self, input_ids, positions, kv_caches, attn_metadata: AttentionMetadata, scratch: Scratch,
                 w4a4: bool = False, embedded: bool = False, kv_scales=None, **kwargs):
         """LlamaModel.forward (quarot_llama.py:484-535) + final norm; returns the normed hidden states [T,H].
         embedded: scratch.hidden[:T] already holds embed_tokens[input_ids] (the engine's bookkeeping launches write it:
         ops.spec_prepare_draft / spec_advance_draft / spec_prepare_verify with embed=...)."""
-        cfg, s, md = self.config, scratch, attn_metadata
-        T = input_ids.numel()
-        eps = cfg.rms_norm_eps
-        hidden = s.hidden[:T]
+        s, T = scratch, input_ids.numel()
+        p = self._plan(T, w4a4, attn_metadata.n_splits, s)
+        self.last_forward_form = p.form   # (tests)
+        tiles = p.xp or p.xp32
+        # what the stages share: the plan, the inputs and the [:T] views of the buffers.  (x, xs): what the norms and the draft
+        # head transform write and the GEMMs read -- int4 rows + scales in the draft pass, fp16 rows in the verify pass; they
+        # and had, the fp16 head transform, are fragment-major tiles in the two tile forms.  act: silu(gate)*up, [T, I]
+        c = SimpleNamespace(p=p, s=s, md=attn_metadata, T=T, positions=positions, eps=self.config.rms_norm_eps, tiles=tiles,
+                            hidden=s.hidden[:T], qkv=s.act_buffer_qkv[:T], attn=s.act_buffer_attn[:T], o=s.act_buffer_output[:T],
+                            gu=s.act_buffer_gate_up[:T], act=s.act_buffer_had_mlp[:T], q3=s.quantized_buffer_mlp[:T],
+                            normed=s.normed[:T], had=s.xp_had if tiles else s.act_buffer_had[:T],
+                            x=s.quantized_buffer_qkv[:T] if w4a4 else (s.xp_normed if tiles else s.normed[:T]),
+                            xs=s.scale_buffer[:T] if w4a4 else None)
         if not embedded:
-            ops.embedding(input_ids, self.embed_tokens, hidden)
-        delta = None
-        qkv, attn, o, gu = s.act_buffer_qkv[:T], s.act_buffer_attn[:T], s.act_buffer_output[:T], s.act_buffer_gate_up[:T]
-        q1, q3, sc = s.quantized_buffer_qkv[:T], s.quantized_buffer_mlp[:T], s.scale_buffer[:T]
-        normed, had, had_mlp = s.normed[:T], s.act_buffer_had[:T], s.act_buffer_had_mlp[:T]
-        row = cfg.q_size + 2 * cfg.kv_size
-        tp_sharded = self.tp is not None and self.tp.world > 1 and getattr(self.tp, "shard_layers", True) and not w4a4
-        # fused GEMM epilogues (decode-sized M)
-        # (head size 64 -- TinyLlama -- has the fused qkv + RoPE + KV-write epilogue on the streaming kernels only)
-        fuse_hd = cfg.head_dim == 128 or (cfg.head_dim == 64 and T <= 32 and
-                                          ops.qkv_rope_linear_supported(w4a4, T, cfg.q_size + 2 * cfg.kv_size, cfg.hidden_size, 64))
-        fuse = fuse_hd and (w4a4 or T <= (min(self.BIG_M, 32) if tp_sharded else self.VERIFY_FUSE_MAX_M))
-        # tensor parallelism only on the verify pass at decode-sized M; the draft pass and prefill run replicated
-        tp_on = tp_sharded and fuse and T <= 32
-        act = s.act_buffer_had_mlp[:T]                            # silu(gate)*up, [T, I]
-        nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        # draft pass at decode-sized M: residual add + LN + int4 quant run in the prologue of the qkv / gate_up GEMM
-        # launches (gemm_stream.hip); the residual stream ping-pongs between two buffers
-        ln_fused = (w4a4 and fuse and self.FUSE_LN and T <= self.FUSE_LN_MAX_M
-                    and ops.ln_linear_s4s4_supported(T, row, cfg.hidden_size)
-                    and ops.ln_linear_s4s4_supported(T, 2 * cfg.intermediate_size, cfg.hidden_size)
-                    and ops.rowwise_scaled_linear_s4s4_residual_supported(T, cfg.hidden_size, cfg.hidden_size)
-                    and ops.rowwise_scaled_linear_s4s4_residual_supported(T, cfg.hidden_size, cfg.intermediate_size))
-        hq = (ln_fused and self.HADAMARD_QUANT_IN_OPROJ and self.MERGE_IN_HADAMARD and md.n_splits <= 64
-              and (ops.heads_hadamard_merged_spread_supported(T, nh, hd) if self.head_had_K == 1 else
-                   ops.heads_hadamard_mix_merged_spread_supported(T, nh, hd, self.head_had_K))
-              and ops.rowwise_scaled_linear_s4s4_residual_hq_supported(T, cfg.hidden_size, cfg.q_size))
-        had16 = s.act_buffer_had[:T]
-        xp = not w4a4 and fuse and not tp_on and self._fragment_major_ok(T, md, s)
-        if xp:
-            normed_x, had_x = s.xp_normed, s.xp_had
-        # verify pass at 17..32 tokens (one GPU): qkv / o_proj / gate_up on the two-token-tile W4A16 streaming kernel over two
-        # fragment-major tiles (fused epilogues as at <= 16 tokens); down_proj stays on the M-tiled kernel (its K passes lose)
-        xp32 = (not w4a4 and not fuse and not tp_sharded and 16 < T <= 32 and self.ACT_FRAGMENT_MAJOR and self.MERGE_IN_HADAMARD
-                and hd == 128 and md.n_splits <= 64 and s.xp_normed is not None and s.xp_normed.shape[0] == 32
-                and ops.w4a16_act_layout32_supported(T, row, cfg.hidden_size)
-                and ops.w4a16_act_layout32_supported(T, cfg.hidden_size, cfg.q_size)
-                and ops.w4a16_act_layout32_supported(T, 2 * cfg.intermediate_size, cfg.hidden_size)
-                and (nh in (32, 64) if self.head_had_K == 1 else
-                     ops.heads_hadamard_mix_merged_spread_supported(T, nh, hd, self.head_had_K)))
-        # ... and down_proj as one-pass K slices of the same kernel across the workgroups, finished inside the next norm
-        S32 = (ops.w4a16_linear_partial_slices_xp32(T, cfg.hidden_size, cfg.intermediate_size)
-               if (xp32 and s.down_part is not None and self.XP32_DOWN_SLICES
-                   and ops.mlp_hadamard_act_layout_supported(T, cfg.intermediate_size, self.had_K)) else 0)
-        if xp32:
-            normed_x, had_x = s.xp_normed, s.xp_had
-        self.last_forward_form = "two-tile" if xp32 else ("fragment-major" if xp else ("fused" if fuse else "unfused"))   # (tests)
-        # draft pass at 17..32 tokens: down_proj as K slices (0 / 1 = the plain launch)
-        S_down = (ops.rowwise_scaled_linear_s4s4_partial_slices(T, cfg.hidden_size, cfg.intermediate_size)
-                  if (w4a4 and fuse and not ln_fused and s.down_ipart is not None and self.DOWN_K_SLICES) else 0)
+            ops.embedding(input_ids, self.embed_tokens, c.hidden)
+        delta = Delta()
         for li, layer in enumerate(self.layers):
             kc, vc = kv_caches[li]
             kvs = self._kv_kw(li, kc, kv_scales)
-            qkv_w, qkv_s = layer.qkv_proj.weight, layer.qkv_proj._scales()
-            gu_w, gu_s = layer.gate_up.weight, layer.gate_up._scales()
-            if ln_fused:
-                # 7 launches per layer; the residual stream is updated in the o_proj / down_proj epilogues
-                # (hidden = residual + proj_out, :380,390), the norms read it in the qkv / gate_up prologues
-                ops.ln_qkv_rope_linear(hidden, None, None, eps, qkv_w, qkv_s, qkv, positions, self.cos_sin_cache,
-                                       kc, vc, md.slot_mapping, nh, nkv, hd, **kvs)                # :373-374,183-226
-                if hq:
-                    # merge + head Hadamard spread over 8 workgroups per token (fp16 + partial row maxima), the Quantizer
-                    # of :235-238 in the o_proj launch's prologue: same bits as the two calls of the else branch
-                    ops.paged_attention(qkv, row, kc, vc, md.block_tables, md.ctx_lens, md.q_start, T, md.max_q_len, nh,
-                                        self.sm_scale, md.n_splits, s.attn_ws, None, **kvs)
-                    if self.head_had_K == 1:
-                        ops.heads_hadamard_merged_spread(s.attn_ws, md.ctx_lens.numel() * md.max_q_len, md.n_splits, T, nh, hd,
-                                                         self.head_had_scale, had16, s.had_part_amax[:T])
-                    else:   # table-factor head count (Llama-2-13B: had40)
-                        ops.heads_hadamard_mix_merged_spread(s.attn_ws, md.ctx_lens.numel() * md.max_q_len, md.n_splits, T, nh,
-                                                             hd, self.head_had, self.head_had_K, self.head_had_scale, had16,
-                                                             s.had_part_amax[:T])
-                    ops.rowwise_scaled_linear_s4s4_residual_hq(had16, s.had_part_amax[:T], 1.0, layer.o_proj.weight,
-                                                               layer.o_proj._scales(), hidden, hidden)
-                else:
-                    self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, q1, sc, None, kvs=kvs)        # :213-238
-                    ops.rowwise_scaled_linear_s4s4_residual(q1, sc, layer.o_proj.weight, layer.o_proj._scales(), hidden, hidden)
-                ops.ln_gate_up_silu_linear(hidden, None, None, eps, gu_w, gu_s, act)                # :380-388,266-284
-                ops.mlp_hadamard(act, self.had_rem_dim, self.had_K, self.mlp_had_scale, q=q3, scale=sc)
-                ops.rowwise_scaled_linear_s4s4_residual(q3, sc, layer.down_proj.weight, layer.down_proj._scales(), hidden, hidden)
-                delta = None
-                continue
-            # input_layernorm (+ residual add of the previous MLP) -> qkv_proj -> rope -> kv write    :373-374,183-226
-            if w4a4:
-                if isinstance(delta, tuple):   # ("ipartial", ...): the previous down_proj's int32 K-slice sums
-                    _, ipart, pxs, pws, S = delta
-                    ops.add_rms_norm_ipartial(hidden, hidden, ipart, pxs, pws, S, eps, q=q1, scale=sc)
-                else:
-                    ops.add_rms_norm_i4(q1, sc, hidden, hidden, delta, eps)
-                x, xs = q1, sc
-            elif xp or xp32:
-                self._add_norm_fp16(normed_x, hidden, delta, eps, xp=True)
-                x, xs = normed_x, None
+            if p.ln_fused:
+                self._ln_fused_layer(c, layer, kc, vc, kvs)
             else:
-                self._add_norm_fp16(normed, hidden, delta, eps)
-                x, xs = normed, None
-            if xp32:
-                ops.qkv_rope_linear_xp32(x, qkv_w, qkv_s, qkv, positions, self.cos_sin_cache, kc, vc, md.slot_mapping, nh, nkv, hd, T,
-                                         **kvs)
-            elif fuse:
-                ops.qkv_rope_linear(x, xs, qkv_w, qkv_s, qkv, positions, self.cos_sin_cache, kc, vc, md.slot_mapping,
-                                    nh, nkv, hd, xp=xp, tokens=T, **kvs)
+                self._norm_qkv(c, layer, kc, vc, kvs, delta)
+                self._attention_o_proj(c, layer, kc, vc, kvs)
+                delta = self._mlp(c, layer)
+        self._add_norm(c, delta, final=True)
+        return c.normed
+
+    def _add_norm(self, c, delta: Delta, final: bool = False):
+        """hidden += delta; then the norm of hidden into (c.x, c.xs) -- the final norm is always fp16 and row-major, in both
+        passes (self.norm(hidden_states) without kwargs, :533)."""
+        hidden, eps = c.hidden, c.eps
+        i4 = c.p.w4a4 and not final
+        out, xp = (c.normed, False) if final else (c.x, c.tiles)
+        if delta.ipart is not None:
+            ops.add_rms_norm_ipartial(hidden, hidden, delta.ipart, delta.x_scale, delta.w_scale, delta.slices, eps,
+                                      q=out if i4 else None, scale=c.xs if i4 else None, out_f16=None if i4 else out)
+        elif delta.part is not None:
+            ops.add_rms_norm_fp16_partial(out, hidden, hidden, delta.part, delta.w_scale, delta.slices, eps, xp=xp)
+        elif i4:
+            ops.add_rms_norm_i4(out, c.xs, hidden, hidden, delta.f16, eps)
+        else:
+            ops.add_rms_norm_fp16(out, hidden, hidden, delta.f16, eps, xp=xp)
+
+    def _attention_hadamard(self, c, kc, vc, kvs, part_amax=None):
+        """Attention + head Hadamard (quarot_llama.py:213-238): + quant into (c.x, c.xs) in the draft pass, fp16 into c.had in the
+        verify pass -- and in the draft pass with part_amax [T, 8], which takes the spread kernels' partial row maxima."""
+        p, md, s, T, cfg = c.p, c.md, c.s, c.T, self.config
+        nh, hd, n_tok = cfg.num_attention_heads, cfg.head_dim, md.ctx_lens.numel() * md.max_q_len
+        spread = part_amax is not None
+        q1, sc = (c.x, c.xs) if p.w4a4 and not spread else (None, None)
+        had = c.had if q1 is None else None
+        # attn None: the head transform merges the context splits; the spread kernels (part_amax) always do, whatever p.heads says
+        attn = c.attn if p.heads == "generic" and not spread else None
+        ops.paged_attention(c.qkv, c.qkv.shape[1], kc, vc, md.block_tables, md.ctx_lens, md.q_start, T, md.max_q_len, nh,
+                            self.sm_scale, md.n_splits, s.attn_ws, attn, **kvs)
+        if self.head_had_K > 1:   # table-factor head count (Llama-2-13B: had40)
+            if attn is None:
+                ops.heads_hadamard_mix_merged_spread(s.attn_ws, n_tok, md.n_splits, T, nh, hd, self.head_had, self.head_had_K,
+                                                     self.head_had_scale, c.had, part_amax, xp=c.tiles)
+            else:   # generic kernels: one workgroup per token
+                ops.heads_hadamard_mix(attn.view(T, nh, hd), self.head_had, self.head_had_K, self.head_had_scale, c.had)
+            if q1 is not None:
+                ops.fuse_sym_quant(c.had, sc, q1)
+        elif spread:
+            ops.heads_hadamard_merged_spread(s.attn_ws, n_tok, md.n_splits, T, nh, hd, self.head_had_scale, had, part_amax)
+        elif attn is None:
+            ops.heads_hadamard_merged(s.attn_ws, n_tok, md.n_splits, T, nh, hd, self.head_had_scale, out_f16=had, q=q1,
+                                      scale=sc, xp=c.tiles)
+        else:
+            ops.heads_hadamard(attn, self.head_had_scale, out_f16=had, q=q1, scale=sc, heads=nh)
+
+    def _ln_fused_layer(self, c, layer, kc, vc, kvs):
+        """The draft layer at <= FUSE_LN_MAX_M tokens, 7 launches: the norms run in the qkv / gate_up prologues, the residual
+        stream is updated in the o_proj / down_proj epilogues (hidden = residual + proj_out, :380,390) -- nothing is handed over."""
+        cfg, md, hidden = self.config, c.md, c.hidden
+        o_w, o_s = layer.o_proj.weight, layer.o_proj._scales()
+        ops.ln_qkv_rope_linear(hidden, None, None, c.eps, layer.qkv_proj.weight, layer.qkv_proj._scales(), c.qkv, c.positions,
+                               self.cos_sin_cache, kc, vc, md.slot_mapping, cfg.num_attention_heads, cfg.num_key_value_heads,
+                               cfg.head_dim, **kvs)                                                 # :373-374,183-226
+        if c.p.hq:
+            amax = c.s.had_part_amax[:c.T]
+            self._attention_hadamard(c, kc, vc, kvs, part_amax=amax)
+            ops.rowwise_scaled_linear_s4s4_residual_hq(c.had, amax, 1.0, o_w, o_s, hidden, hidden)
+        else:
+            self._attention_hadamard(c, kc, vc, kvs)                                                # :213-238
+            ops.rowwise_scaled_linear_s4s4_residual(c.x, c.xs, o_w, o_s, hidden, hidden)
+        ops.ln_gate_up_silu_linear(hidden, None, None, c.eps, layer.gate_up.weight, layer.gate_up._scales(), c.act)   # :380-388,266-284
+        ops.mlp_hadamard(c.act, self.had_rem_dim, self.had_K, self.mlp_had_scale, q=c.q3, scale=c.xs)
+        ops.rowwise_scaled_linear_s4s4_residual(c.q3, c.xs, layer.down_proj.weight, layer.down_proj._scales(), hidden, hidden)
+
+    def _norm_qkv(self, c, layer, kc, vc, kvs, delta: Delta):
+        """input_layernorm (+ residual add of the previous MLP) -> qkv_proj -> rope -> kv write    :373-374,183-226"""
+        p, cfg, md = c.p, self.config, c.md
+        nh, nkv, hd = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        w, w_s = layer.qkv_proj.weight, layer.qkv_proj._scales()
+        self._add_norm(c, delta)
+        if p.xp32:
+            ops.qkv_rope_linear_xp32(c.x, w, w_s, c.qkv, c.positions, self.cos_sin_cache, kc, vc, md.slot_mapping, nh, nkv, hd,
+                                     c.T, **kvs)
+        elif p.fuse:
+            ops.qkv_rope_linear(c.x, c.xs, w, w_s, c.qkv, c.positions, self.cos_sin_cache, kc, vc, md.slot_mapping, nh, nkv, hd,
+                                xp=p.xp, tokens=c.T, **kvs)
+        else:
+            if p.w4a4:
+                ops.rowwise_scaled_linear_cutlass_s4s4_unified(c.x, c.xs, w, w_s, None, c.qkv)
             else:
-                if w4a4:
-                    ops.rowwise_scaled_linear_cutlass_s4s4_unified(q1, sc, qkv_w, qkv_s, None, qkv)
-                else:
-                    self._w4a16(normed, layer.qkv_proj, qkv)
-                ops.rope_kv_write(positions, qkv, self.cos_sin_cache, kc, vc, md.slot_mapping, nh, nkv, hd, **kvs)
-            # attention -> heads hadamard (+ quant) -> o_proj -> residual + post_attention_layernorm     :231-243,380-387
-            if w4a4:
-                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, q1, sc, None, kvs=kvs)
-                ops.rowwise_scaled_linear_cutlass_s4s4_unified(q1, sc, layer.o_proj.weight, layer.o_proj._scales(), None, o)
-                ops.add_rms_norm_i4(q1, sc, hidden, hidden, o, eps)
-                x, xs = q1, sc
-            elif xp:
-                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, None, None, had_x, xp=True, kvs=kvs)
-                self._w4a16(had_x, layer.o_proj, o, xp=True, tokens=T)
-                ops.add_rms_norm_fp16(normed_x, hidden, hidden, o, eps, xp=True)
-                x, xs = normed_x, None
-            elif xp32:
-                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, None, None, had_x, xp=True, kvs=kvs)
-                ops.w4a16_linear_xp32(had_x, layer.o_proj.weight, layer.o_proj._scales(), o, T)
-                ops.add_rms_norm_fp16(normed_x, hidden, hidden, o, eps, xp=True)
-                x, xs = normed_x, None
+                ops.w4a16_linear(c.x, w, w_s, c.qkv)   # (every M reads the packed int4 buffer: streaming / M-tiled kernel)
+            ops.rope_kv_write(c.positions, c.qkv, self.cos_sin_cache, kc, vc, md.slot_mapping, nh, nkv, hd, **kvs)
+
+    def _attention_o_proj(self, c, layer, kc, vc, kvs):
+        """attention -> heads hadamard (+ quant) -> o_proj -> residual + post_attention_layernorm     :231-243,380-387"""
+        w, w_s = layer.o_proj.weight, layer.o_proj._scales()
+        self._attention_hadamard(c, kc, vc, kvs)
+        delta = Delta(f16=c.o)
+        if c.p.w4a4:
+            ops.rowwise_scaled_linear_cutlass_s4s4_unified(c.x, c.xs, w, w_s, None, c.o)
+        elif c.p.xp32:
+            ops.w4a16_linear_xp32(c.had, w, w_s, c.o, c.T)
+        else:
+            delta = self._w4a16_delta(c, c.had, layer.o_proj, c.p.S_o)
+        self._add_norm(c, delta)
+
+    def _w4a16_delta(self, c, x, lin, S: int) -> Delta:
+        """A verify-pass projection whose output the next norm adds: row-parallel under tensor parallelism, as S K slices
+        whose raw sums the norm finishes, or plain."""
+        w, w_s, T = lin.weight, lin._scales(), c.T
+        if c.p.tp_on:   # this rank's K range: raw fp32 sums, all-reduce in fp32; scale + ONE fp16 rounding + add inside the norm
+            k0, k1 = self.tp.k_range(2 * w.shape[1])   # K: two int4 weights per packed byte
+            part = c.s.tp_part[:, :T]
+            ops.w4a16_linear_ksliced_raw(x, w, part[0], k0, k1)
+            self.tp.all_reduce(part)
+            return Delta(part=part, w_scale=w_s, slices=1)
+        if S:
+            part = c.s.k_slices(S, T)
+            ops.w4a16_linear_partial(x, w, part, S, xp=c.p.xp, tokens=T)
+            return Delta(part=part, w_scale=w_s, slices=S)
+        ops.w4a16_linear(x, w, w_s, c.o, xp=c.p.xp, tokens=T)
+        return Delta(f16=c.o)
+
+    def _mlp(self, c, layer) -> Delta:
+        """gate_up -> silu*up -> online hadamard (+ quant) -> down_proj; returns what the next norm adds     :266-299"""
+        p, s, T, I = c.p, c.s, c.T, self.config.intermediate_size
+        g_w, g_s = layer.gate_up.weight, layer.gate_up._scales()
+        w, w_s = layer.down_proj.weight, layer.down_proj._scales()
+        had = (self.had_rem_dim, self.had_K, self.mlp_had_scale)
+        if p.xp32:
+            ops.gate_up_silu_linear_xp32(c.x, g_w, g_s, c.act, T)
+        elif p.tp_on:   # column-parallel gate_up: own channels of [T, I], then all-gather of the channel ranges
+            c0, c1 = self.tp.channel_range(I)
+            ops.gate_up_silu_linear_shard(c.x, g_w, g_s, c.act, c0, c1 - c0)
+            self.tp.all_gather_channels(c.act, I)
+        elif p.fuse:
+            ops.gate_up_silu_linear(c.x, c.xs, g_w, g_s, c.act, xp=p.xp, tokens=T)
+        elif p.w4a4:
+            ops.rowwise_scaled_linear_cutlass_s4s4_unified(c.x, c.xs, g_w, g_s, None, c.gu)
+        else:
+            ops.w4a16_linear(c.x, g_w, g_s, c.gu)
+        if p.w4a4:   # (K-sliced down_proj: its activation scales outlive the next norm's, so they get their own buffer)
+            xs = s.down_xs[:T] if p.S_down else c.xs
+            if p.fuse:
+                ops.mlp_hadamard(c.act, *had, q=c.q3, scale=xs)
             else:
-                self._attention_hadamard(qkv, row, kc, vc, md, T, s, attn, None, None, had, kvs=kvs)
-                if tp_on:   # row-parallel o_proj over this rank's K range of the shared buffer: raw fp32 sums,
-                    # all-reduce in fp32, then scale + ONE fp16 rounding + residual add inside the norm (as on one GPU)
-                    k0, k1 = self.tp.k_range(cfg.hidden_size)
-                    part = s.tp_part[:, :T]
-                    ops.w4a16_linear_ksliced_raw(had, layer.o_proj.weight, part[0], k0, k1)
-                    self.tp.all_reduce(part)
-                    ops.add_rms_norm_fp16_partial(normed, hidden, hidden, part, layer.o_proj._scales(), 1, eps)
-                elif self.VERIFY_O_SLICES > 1 and fuse and s.down_part is not None and T <= 16:
-                    # dev knob (QSPEC_VERIFY_O_SLICES = 2 / 4): o_proj as K slices whose raw sums the norm finishes, as
-                    # down_proj's are -- measured, not the default (DESIGN.md section 4): the slice order of the sum also
-                    # breaks the bit identity with the module-wise path
-                    S = self.VERIFY_O_SLICES
-                    part = s.down_part.view(-1)[:S * T * cfg.hidden_size].view(S, T, cfg.hidden_size)
-                    ops.w4a16_linear_partial(had, layer.o_proj.weight, part, S)
-                    ops.add_rms_norm_fp16_partial(normed, hidden, hidden, part, layer.o_proj._scales(), S, eps)
-                else:
-                    # 17+ tokens: where the M-tiled kernel's plan slices K (narrow layers), the raw sums are finished inside
-                    # the norm instead of by a finishing launch of their own (same expression, same bits)
-                    S_o = (ops.w4a16_linear_partial_slices(T, cfg.hidden_size, cfg.q_size)
-                           if (T > 16 and s.down_part is not None and self.TILED_PARTIAL_IN_NORM) else 0)
-                    if 1 < S_o <= 8:
-                        part = s.down_part.view(-1)[:S_o * T * cfg.hidden_size].view(S_o, T, cfg.hidden_size)
-                        ops.w4a16_linear_partial(had, layer.o_proj.weight, part, S_o)
-                        ops.add_rms_norm_fp16_partial(normed, hidden, hidden, part, layer.o_proj._scales(), S_o, eps)
-                    else:
-                        self._w4a16(had, layer.o_proj, o)
-                        ops.add_rms_norm_fp16(normed, hidden, hidden, o, eps)
-                x, xs = normed, None
-            # gate_up -> silu*up -> online hadamard (+ quant) -> down_proj                              :266-299
-            if xp32:
-                ops.gate_up_silu_linear_xp32(x, gu_w, gu_s, act, T)
-                if 1 < S32 <= 8:
-                    ops.mlp_hadamard(act, self.had_rem_dim, self.had_K, self.mlp_had_scale, out_f16=s.xp_had_mlp, xp=True)
-                    part = s.down_part.view(-1)[:S32 * T * cfg.hidden_size].view(S32, T, cfg.hidden_size)
-                    ops.w4a16_linear_partial_xp32(s.xp_had_mlp, layer.down_proj.weight, part, S32, T)
-                    delta = ("partial", part, layer.down_proj._scales(), S32)
-                    continue
-                had_mlp_in = s.act_buffer_gate_up.view(-1)[:T * cfg.intermediate_size].view(T, cfg.intermediate_size)
-                ops.mlp_hadamard(act, self.had_rem_dim, self.had_K, self.mlp_had_scale, out_f16=had_mlp_in)
-            elif fuse:
-                if tp_on:   # column-parallel gate_up: own channels of [T, I], then all-gather of the channel ranges
-                    c0, c1 = self.tp.channel_range(cfg.intermediate_size)
-                    ops.gate_up_silu_linear_shard(x, gu_w, gu_s, act, c0, c1 - c0)
-                    self.tp.all_gather_channels(act, cfg.intermediate_size)
-                else:
-                    ops.gate_up_silu_linear(x, xs, gu_w, gu_s, act, xp=xp, tokens=T)
-                if w4a4:   # (K-sliced down_proj: its activation scales outlive the next norm's, so they get their own buffer)
-                    ops.mlp_hadamard(act, self.had_rem_dim, self.had_K, self.mlp_had_scale, q=q3,
-                                     scale=s.down_xs[:T] if S_down > 1 else sc)
-                elif xp:
-                    had_mlp_in = s.xp_had_mlp
-                    ops.mlp_hadamard(act, self.had_rem_dim, self.had_K, self.mlp_had_scale, out_f16=had_mlp_in, xp=True)
-                else:
-                    had_mlp_in = s.act_buffer_gate_up.view(-1)[:T * cfg.intermediate_size].view(T, cfg.intermediate_size)
-                    ops.mlp_hadamard(act, self.had_rem_dim, self.had_K, self.mlp_had_scale, out_f16=had_mlp_in)
-            else:
-                if w4a4:
-                    ops.rowwise_scaled_linear_cutlass_s4s4_unified(q1, sc, gu_w, gu_s, None, gu)
-                    ops.silu_mul_hadamard(gu, self.had_rem_dim, self.had_K, self.mlp_had_scale, q=q3, scale=sc)
-                else:
-                    self._w4a16(normed, layer.gate_up, gu)
-                    ops.silu_mul_hadamard(gu, self.had_rem_dim, self.had_K, self.mlp_had_scale, out_f16=had_mlp)
-                    had_mlp_in = had_mlp
-            if w4a4:
-                if S_down > 1:   # 17..32 tokens: K slices, int32 sums finished inside the next norm (ops.add_rms_norm_ipartial)
-                    ipart = s.down_ipart.view(-1)[:S_down * T * cfg.hidden_size].view(S_down, T, cfg.hidden_size)
-                    ops.rowwise_scaled_linear_s4s4_partial(q3, layer.down_proj.weight, ipart, S_down)
-                    delta = ("ipartial", ipart, s.down_xs[:T], layer.down_proj._scales(), S_down)
-                    continue
-                ops.rowwise_scaled_linear_cutlass_s4s4_unified(q3, sc, layer.down_proj.weight, layer.down_proj._scales(), None, o)
-            elif tp_on:     # row-parallel down_proj: raw fp32 sums, finished by the next norm
-                k0, k1 = self.tp.k_range(cfg.intermediate_size)
-                part = s.tp_part[:, :T]
-                ops.w4a16_linear_ksliced_raw(had_mlp_in, layer.down_proj.weight, part[0], k0, k1)
-                self.tp.all_reduce(part)
-                delta = ("partial", part, layer.down_proj._scales(), 1)
-                continue
-            else:
-                S = 0
-                if s.down_part is not None and (fuse or (T > 16 and self.TILED_PARTIAL_IN_NORM)):
-                    # long K at decode-sized M (streaming kernel) / narrow layer at 17+ tokens (M-tiled kernel's plan):
-                    # K slices, finished by the next norm
-                    S = ops.w4a16_linear_partial_slices(T, cfg.hidden_size, cfg.intermediate_size)
-                if 0 < S <= (4 if T <= 16 else 8):
-                    part = s.down_part.view(-1)[:S * T * cfg.hidden_size].view(S, T, cfg.hidden_size)
-                    ops.w4a16_linear_partial(had_mlp_in, layer.down_proj.weight, part, S, xp=xp, tokens=T)
-                    delta = ("partial", part, layer.down_proj._scales(), S)
-                    continue
-                self._w4a16(had_mlp_in, layer.down_proj, o, xp=xp, tokens=T)
-            delta = o
-        # final norm is always fp16, in both passes (self.norm(hidden_states) without kwargs, :533)
-        self._add_norm_fp16(normed, hidden, delta, eps)
-        return normed
+                ops.silu_mul_hadamard(c.gu, *had, q=c.q3, scale=xs)
+            if p.S_down:   # 17..32 tokens: K slices, int32 sums finished inside the next norm (ops.add_rms_norm_ipartial)
+                ipart = s.k_slices(p.S_down, T, int32=True)
+                ops.rowwise_scaled_linear_s4s4_partial(c.q3, w, ipart, p.S_down)
+                return Delta(ipart=ipart, x_scale=xs, w_scale=w_s, slices=p.S_down)
+            ops.rowwise_scaled_linear_cutlass_s4s4_unified(c.q3, xs, w, w_s, None, c.o)
+            return Delta(f16=c.o)
+        if p.xp or p.S32:
+            y = s.xp_had_mlp
+            ops.mlp_hadamard(c.act, *had, out_f16=y, xp=True)
+        elif p.fuse or p.xp32:
+            y = s.mlp_rows(T)
+            ops.mlp_hadamard(c.act, *had, out_f16=y)
+        else:
+            y = c.act
+            ops.silu_mul_hadamard(c.gu, *had, out_f16=y)
+        if p.S32:
+            part = s.k_slices(p.S32, T)
+            ops.w4a16_linear_partial_xp32(y, w, part, p.S32, T)
+            return Delta(part=part, w_scale=w_s, slices=p.S32)
+        return self._w4a16_delta(c, y, layer.down_proj, p.S_mlp)
 
     def compute_logits(self, hidden_states, scratch: Scratch, shard_vocab: bool = False):
         """LogitsProcessor with a plain nn.Linear lm_head (vllm/model_executor/layers/logits_processor.py:92-97).

@@ -715,7 +715,7 @@ def test_fragment_major_activation_tiles_change_no_bit(family, ctx_lens, q_len, 
     rng = np.random.default_rng(6)
     inp = make_inputs(model, rng, ctx_lens, q_len)
     s = Scratch(cfg, inp["T"], len(ctx_lens), q_len, inp["n_splits"], DEV)
-    assert model._fragment_major_ok(inp["T"], inp["md"], s) == (family != "llama-3-70b")
+    assert model._plan(inp["T"], False, inp["md"].n_splits, s).xp == (family != "llama-3-70b")
     outs = []
     for on in (True, False):
         monkeypatch.setattr(model, "ACT_FRAGMENT_MAJOR", on)
