@@ -630,6 +630,25 @@ int qspec_spec_snapshot(int batch, int restore, int32_t* seq_lens, int32_t* gen_
 int qspec_collect_error_words(int32_t* w0, int32_t* w1, int32_t* w2, int32_t* w3, int clear, int64_t* out,
                               void* stream);
 
+/* Logprobs (vllm/model_executor/layers/sampler.py:284, _get_ranks :861-879, get_logprobs :882 ff.): per row r of x
+ * [rows, vocab] (row r starts at x + r * row_stride elements, row_stride >= vocab; what lies between the rows is never read)
+ *   token_logprob[r] = lp(token_ids[r]),  token_rank[r] = 1 + #{v : x[v] > x[token_ids[r]]}  (strict compare on the inputs),
+ *   top_ids / top_logprobs [rows, num_top]: the num_top largest inputs in descending order, ties lowest id first, and their lp;
+ *   with num_top > vocab the surplus entries are id -1 and logprob -inf.  0 <= num_top <= QS_MAX_LOGPROBS; the two top
+ *   pointers may be NULL when num_top is 0.
+ *   A token id outside [0, vocab) gives token_logprob 0.0f and token_rank -1 (the dummy entry); the row's top is still written.
+ * from_probs:  x = the processed probabilities (fp32), lp(v) = logf(max(x[v], FLT_MIN)).
+ * from_logits: x = raw logits (fp16), lp(v) = float(x[v]) - lse, lse = m + logf(sum_v expf(float(x[v]) - m)), m the row
+ *   maximum, all in fp32 (torch.log_softmax(logits.float(), -1)).
+ * One launch, one workgroup per row, no workspace.  rows == 0 is a no-op.  NaN inputs give unspecified values, in bounds. */
+#define QS_MAX_LOGPROBS 32
+int qspec_token_logprobs_from_probs(const float* probs, int64_t row_stride, const int64_t* token_ids, int rows, int vocab,
+                                    int num_top, float* token_logprob, int32_t* token_rank, int32_t* top_ids,
+                                    float* top_logprobs, void* stream);
+int qspec_token_logprobs_from_logits(const qspec_half* logits, int64_t row_stride, const int64_t* token_ids, int rows, int vocab,
+                                     int num_top, float* token_logprob, int32_t* token_rank, int32_t* top_ids,
+                                     float* top_logprobs, void* stream);
+
 /* Activation layout of the verify pass at <= 16 tokens (no reference counterpart: the reference's fp16 GEMM is
  * bitblas.Matmul on row-major x, quarot_nn/linear.py:122).  The W4A16 GEMMs above consume x as v_mfma_f32_16x16x32_f16
  * operand fragments; reading row-major x means one pass through LDS per launch to regroup it.  The `_xp` twins below

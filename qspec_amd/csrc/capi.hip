@@ -810,6 +810,35 @@ int qspec_collect_error_words(int32_t* w0, int32_t* w1, int32_t* w2, int32_t* w3
     return finish(op, qspec::collect_error_words(w0, w1, w2, w3, clear, out, ST));
 }
 
+// logprobs (logprobs.hip): one body for both entry points; LOGITS selects the kernel's input form (fp16 logits / fp32 probs)
+static int token_logprobs(const char* op, bool LOGITS, const void* x, int64_t row_stride, const int64_t* token_ids, int rows, int vocab, int num_top,
+                          float* token_logprob, int32_t* token_rank, int32_t* top_ids, float* top_logprobs, void* stream) {
+    if (rows < 0) return fail("%s: rows < 0", op);
+    if (vocab < 1) return fail("%s: vocab = %d < 1", op, vocab);
+    if (num_top < 0 || num_top > QS_MAX_LOGPROBS) return fail("%s: num_top = %d outside 0..%d", op, num_top, QS_MAX_LOGPROBS);
+    if (row_stride < vocab) return fail("%s: row_stride = %lld < vocab = %d", op, (long long)row_stride, vocab);
+    if (rows == 0) return 0;
+    NONNULL(op, x); NONNULL(op, token_ids); NONNULL(op, token_logprob); NONNULL(op, token_rank);
+    if (num_top > 0) { NONNULL(op, top_ids); NONNULL(op, top_logprobs); }
+    if (LOGITS)
+        return finish(op, qspec::token_logprobs_from_logits(reinterpret_cast<const f16*>(x), row_stride, token_ids, rows, vocab,
+                                                            num_top, token_logprob, token_rank, top_ids, top_logprobs, ST));
+    return finish(op, qspec::token_logprobs_from_probs(reinterpret_cast<const float*>(x), row_stride, token_ids, rows, vocab, num_top,
+                                                       token_logprob, token_rank, top_ids, top_logprobs, ST));
+}
+int qspec_token_logprobs_from_probs(const float* probs, int64_t row_stride, const int64_t* token_ids, int rows, int vocab,
+                                    int num_top, float* token_logprob, int32_t* token_rank, int32_t* top_ids, float* top_logprobs,
+                                    void* stream) {
+    return token_logprobs("qspec_token_logprobs_from_probs", false, probs, row_stride, token_ids, rows, vocab, num_top,
+                                 token_logprob, token_rank, top_ids, top_logprobs, stream);
+}
+int qspec_token_logprobs_from_logits(const qspec_half* logits, int64_t row_stride, const int64_t* token_ids, int rows, int vocab,
+                                     int num_top, float* token_logprob, int32_t* token_rank, int32_t* top_ids, float* top_logprobs,
+                                     void* stream) {
+    return token_logprobs("qspec_token_logprobs_from_logits", true, logits, row_stride, token_ids, rows, vocab, num_top,
+                                token_logprob, token_rank, top_ids, top_logprobs, stream);
+}
+
 size_t qspec_xwg_workspace_bytes(void) { return qspec::xwg_workspace_bytes(); }
 int qspec_mlp_hadamard(const qspec_half* act, const qspec_half* hadK, qspec_half* out_f16, int8_t* q, qspec_half* scale,
                        float had_scale, float clip_ratio, int tokens, int intermediate, int K, void* workspace,

@@ -264,4 +264,11 @@ int spec_snapshot(int B, int restore, int32_t* seq_lens, int32_t* gen_lens, int6
 int collect_error_words(int32_t* w0, int32_t* w1, int32_t* w2, int32_t* w3, int clear, int64_t* out, hipStream_t st);
 int spec_commit(int B, int k, const int64_t* out_tokens, int32_t* seq_lens, int64_t* last_token, int64_t* gen_tokens,
                 int32_t* gen_lens, int gen_cap, hipStream_t st);
+
+// logprobs.hip: the selected token's logprob and rank + the num_top best of every row, from the processed probabilities
+// (fp32) or from raw logits (fp16); one launch, no workspace
+int token_logprobs_from_probs(const float* probs, int64_t row_stride, const int64_t* token_ids, int rows, int vocab, int num_top,
+                              float* token_logprob, int32_t* token_rank, int32_t* top_ids, float* top_logprobs, hipStream_t st);
+int token_logprobs_from_logits(const f16* logits, int64_t row_stride, const int64_t* token_ids, int rows, int vocab, int num_top,
+                               float* token_logprob, int32_t* token_rank, int32_t* top_ids, float* top_logprobs, hipStream_t st);
 }  // namespace qspec

@@ -809,6 +809,41 @@ def sample_top_k_top_p(logits, probs, token, temperature=None, top_k=None, top_p
               draw_stream, ws.data_ptr(), _stream())
 
 
+# ------------------------------------------------------------------ logprobs (include/qspec_hip.h, "Logprobs")
+MAX_LOGPROBS = 32   # QS_MAX_LOGPROBS
+
+
+def _token_logprobs(entry, x, dtype, token_ids, num_top: int, token_logprob, token_rank, top_ids, top_logprobs):
+    if x.dim() != 2 or x.stride(1) != 1 or x.dtype != dtype or not x.is_cuda:
+        raise RuntimeError(f"x must be a [rows, vocab] {dtype} HIP tensor with unit inner stride (rows may be strided: no CPU "
+                           "fallback, no copy)")
+    rows, vocab = x.shape
+    if not 0 <= num_top <= MAX_LOGPROBS:
+        raise ValueError(f"num_top = {num_top} outside 0..{MAX_LOGPROBS}")
+    for t, name, n in ((token_ids, "token_ids", rows), (token_logprob, "token_logprob", rows), (token_rank, "token_rank", rows)) \
+            + (((top_ids, "top_ids", rows * num_top), (top_logprobs, "top_logprobs", rows * num_top)) if num_top else ()):
+        if t is None or t.numel() < n:
+            raise RuntimeError(f"{name} needs {n} entries")
+    _call(entry, x.data_ptr(), x.stride(0) if rows > 1 else max(x.stride(0), vocab), _chk(token_ids, "token_ids", _I64), rows, vocab,
+          num_top, _chk(token_logprob, "token_logprob", _F32), _chk(token_rank, "token_rank", _I32),
+          _chk(top_ids, "top_ids", _I32) if num_top else None, _chk(top_logprobs, "top_logprobs", _F32) if num_top else None,
+          _stream())
+
+
+def token_logprobs_from_probs(probs, token_ids, num_top: int, token_logprob, token_rank, top_ids=None, top_logprobs=None):
+    """Sampler logprobs of the PROCESSED distribution (sampler.py:284, _get_ranks :861-879, get_logprobs :882 ff.): per row of
+    probs [rows, V] fp32 the logprob logf(max(p, FLT_MIN)) and rank of token_ids[row] (int64; outside [0, V): 0.0 / -1) and the
+    num_top most probable ids (int32, ties lowest id first) with their logprobs -- qspec_token_logprobs_from_probs."""
+    _token_logprobs("qspec_token_logprobs_from_probs", probs, _F32, token_ids, num_top, token_logprob, token_rank, top_ids,
+                    top_logprobs)
+
+
+def token_logprobs_from_logits(logits, token_ids, num_top: int, token_logprob, token_rank, top_ids=None, top_logprobs=None):
+    """The same from raw fp16 logits [rows, V]: lp = log_softmax(logits.float(), -1) -- qspec_token_logprobs_from_logits."""
+    _token_logprobs("qspec_token_logprobs_from_logits", logits, _F16, token_ids, num_top, token_logprob, token_rank, top_ids,
+                    top_logprobs)
+
+
 # ------------------------------------------------------------------ logit processors (include/qspec_hip.h, "logit processors")
 MAX_STOP_IDS = 16   # QS_MAX_STOP_IDS
 

@@ -25,6 +25,7 @@ exact after `sync_lens()` (the worker syncs once per cycle anyway) and grows by 
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
 import os
@@ -191,6 +192,13 @@ class QSpecEngine:
     # the embedding lookups of the cycle's four forwards ride in the bookkeeping launches in front of them (5 launches less)
     EMBED_IN_BOOKKEEPING = os.environ.get("QSPEC_EMBED_IN_BOOKKEEPING", "1") != "0"
     PREFILL_TOKEN_BUDGET = 4096   # tokens per prompt-pass forward when several requests are admitted together
+    PROMPT_LOGPROB_ROWS = 256     # prompt rows per lm_head launch of the prompt logprobs (ONE fp16 [rows, V] buffer, made at first use)
+    # logprobs (token_logprobs / take_prompt_logprobs): everything below stays None until a request asks for them
+    _first_probs: Optional[dict] = None       # slot -> (the processed distribution its first token was sampled from, row)
+    _prompt_results: Optional[dict] = None    # slot -> host tensors waiting for take_prompt_logprobs()
+    _plp_logits: Optional[torch.Tensor] = None
+    _lp_dev: Optional[torch.Tensor] = None    # one int32 device buffer for a call's four outputs, and its pinned host twin
+    _lp_host: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ prefill (_run_no_spec, :666-720)
     @torch.no_grad()
@@ -203,10 +211,14 @@ class QSpecEngine:
     @torch.no_grad()
     def add_sequences_to(self, slots: Sequence[int], prompts: Sequence[Sequence[int]],
                          block_tables: Optional[Sequence[Optional[Sequence[int]]]] = None,
-                         num_prompt_tokens: Optional[Sequence[Optional[int]]] = None) -> None:
+                         num_prompt_tokens: Optional[Sequence[Optional[int]]] = None,
+                         prompt_logprobs: Optional[Sequence[Optional[int]]] = None) -> None:
         """Admit several requests at once: one W4A16 forward over the concatenated prompts (flash-attn varlen form).
         num_prompt_tokens[i] (None: all of it): how many tokens of prompts[i] are the request's PROMPT -- a preempted
-        request comes back with prompt + outputs as one token list, and the penalties / min_tokens tell the two apart."""
+        request comes back with prompt + outputs as one token list, and the penalties / min_tokens tell the two apart.
+        prompt_logprobs[i] (None: not asked for): SamplingParams.prompt_logprobs of request i -- the logprob and rank of every
+        token of prompts[i] but the first plus that many best, from the RAW target logits; take_prompt_logprobs(slot) hands
+        them over."""
         cfg, dev = self.cfg, self.device
         n = len(slots)
         if n == 0:
@@ -230,9 +242,12 @@ class QSpecEngine:
         for i in range(n):
             if npts[i] is not None and not 1 <= npts[i] <= len(prompts[i]):
                 raise ValueError(f"num_prompt_tokens {npts[i]} outside 1..{len(prompts[i])}")
+        plps = [None] * n if prompt_logprobs is None else list(prompt_logprobs)
+        for v in plps:
+            self._check_num_top(v)
         if n == 1:
             self.add_sequence(slots[0], prompts[0], None if block_tables is None else block_tables[0],
-                              num_prompt_tokens=npts[0])
+                              num_prompt_tokens=npts[0], prompt_logprobs=plps[0])
             return
         if sum(len(p) for p in prompts) > self.PREFILL_TOKEN_BUDGET:
             # several passes of at most PREFILL_TOKEN_BUDGET tokens (measured: 4 x 512 tokens in one pass 37 ms vs 49 ms
@@ -242,7 +257,7 @@ class QSpecEngine:
                 if i == n or (group and tokens + len(prompts[i]) > self.PREFILL_TOKEN_BUDGET):
                     self.add_sequences_to([slots[j] for j in group], [prompts[j] for j in group],
                                           None if block_tables is None else [block_tables[j] for j in group],
-                                          [npts[j] for j in group])
+                                          [npts[j] for j in group], [plps[j] for j in group])
                     group, tokens = [], 0
                 if i < n:
                     group.append(i)
@@ -265,13 +280,18 @@ class QSpecEngine:
         for i, b in enumerate(slots):
             self.sampling.admit_tokens(b, prompts[i], npts[i])
         self._first_token(hs[last].contiguous(), s, list(slots), lens)
+        starts = q_start.tolist() if any(v is not None for v in plps) else None
+        for i, b in enumerate(slots):
+            if plps[i] is not None:
+                self._prompt_logprobs(b, hs[starts[i]:starts[i] + lens[i] - 1], prompts[i], plps[i])
         torch.cuda.synchronize()
 
     @torch.no_grad()
     def add_sequence(self, slot: int, prompt: Sequence[int], block_table: Optional[Sequence[int]] = None,
-                     sync: bool = True, num_prompt_tokens: Optional[int] = None) -> None:
+                     sync: bool = True, num_prompt_tokens: Optional[int] = None, prompt_logprobs: Optional[int] = None) -> None:
         """Admit a request into an empty slot: scorer-only W4A16 prompt pass (the proposer never runs on prefill,
-        spec_decode_worker.py:699); the first generated token is the target's greedy token."""
+        spec_decode_worker.py:699); the first generated token is the target's greedy token.  prompt_logprobs: see
+        add_sequences_to."""
         cfg, dev, b = self.cfg, self.device, slot
         if not 0 <= b < self.B:
             raise ValueError(f"slot {b} outside the captured batch of {self.B}")
@@ -279,6 +299,7 @@ class QSpecEngine:
             raise ValueError(f"slot {b} is occupied; free_slot() it first")
         if num_prompt_tokens is not None and not 1 <= num_prompt_tokens <= len(prompt):
             raise ValueError(f"num_prompt_tokens {num_prompt_tokens} outside 1..{len(prompt)}")
+        self._check_num_top(prompt_logprobs)
         if block_table is not None:
             self.set_block_table(b, block_table)
         T = len(prompt)
@@ -297,6 +318,8 @@ class QSpecEngine:
         hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False, **self._kv_fw)
         self.sampling.admit_tokens(b, prompt, num_prompt_tokens)
         self._first_token(hs[T - 1:T], s, [b], [T])
+        if prompt_logprobs is not None:
+            self._prompt_logprobs(b, hs[:T - 1], prompt, prompt_logprobs)
         if sync:
             torch.cuda.synchronize()
 
@@ -310,7 +333,10 @@ class QSpecEngine:
         rows = self.sampling.gathered_rows(slots, level, not greedy, scratch.logits[:n])
         base_pos = None if greedy else torch.tensor(prompt_lens, dtype=torch.int32, device=self.device)
         self._sample(level, rows, hs, scratch, probs, tok, base_pos=base_pos, argmax=greedy)
+        if self._first_probs is None:
+            self._first_probs = {}
         for i, (b, T) in enumerate(zip(slots, prompt_lens)):   # the slots are occupied from here on
+            self._first_probs[b] = (probs, i)   # kept for token_logprobs("first"); free_slot / the next admission drops it
             self.seq_lens[b] = T + 1
             self.last_token[b] = tok[i]
             self.gen_tokens[b].fill_(-1)
@@ -354,6 +380,9 @@ class QSpecEngine:
         self.gen_lens[slot] = 0
         self._len_ub[slot] = 0
         self._gen_ub[slot] = 0
+        for kept in (self._first_probs, self._prompt_results):
+            if kept:
+                kept.pop(slot, None)
         self.set_sampling_params(slot)          # back to greedy, no seed
         if self._bt_host[slot] is not None:
             # the request's blocks go back to the scheduler: the slot must not keep a table (and a capacity) that the
@@ -368,6 +397,97 @@ class QSpecEngine:
                 self._capacity[slot] = 0
             self._bt_host[slot] = None
         self.n_active = sum(1 for v in self._len_ub if v > 0)
+
+    # ------------------------------------------------------------------ logprobs (sampler.py:284, :861-879, :882 ff.)
+    @staticmethod
+    def _check_num_top(num_top: Optional[int]) -> None:
+        if num_top is not None and not 0 <= int(num_top) <= ops.MAX_LOGPROBS:
+            raise ValueError(f"{num_top} logprobs asked for: 0..{ops.MAX_LOGPROBS} are supported")
+
+    def _logprob_buffers(self, rows: int, num_top: int):
+        """(logprob [rows] f32, rank [rows] i32, top ids [rows * num_top] i32, top logprobs [rows * num_top] f32) as views of
+        ONE device buffer, and the matching pinned host views: a call's results come back in one copy.  Made at first use."""
+        need = rows * (2 + 2 * num_top)
+        if self._lp_dev is None or self._lp_dev.numel() < need:
+            self._lp_dev = torch.empty(need, dtype=torch.int32, device=self.device)
+            self._lp_host = torch.empty(need, dtype=torch.int32, pin_memory=(self.device.type == "cuda"))
+
+        def views(buf):
+            n = rows * num_top
+            return (buf[:rows].view(torch.float32), buf[rows:2 * rows], buf[2 * rows:2 * rows + n],
+                    buf[2 * rows + n:2 * rows + 2 * n].view(torch.float32))
+        return views(self._lp_dev), views(self._lp_host), need
+
+    def _read_logprobs(self, host, need: int, shape, num_top: int):
+        self._lp_host[:need].copy_(self._lp_dev[:need], non_blocking=True)
+        if self.device.type == "cuda":
+            torch.cuda.current_stream(self.device).synchronize()
+        lp, rank, ids, tlp = host
+        return lp.clone().view(*shape), rank.clone().view(*shape), ids.clone().view(*shape, num_top), tlp.clone().view(*shape, num_top)
+
+    @torch.no_grad()
+    def token_logprobs(self, kind: str, slots: Sequence[int], token_ids, num_top: int = 0):
+        """Logprob, rank and the num_top best of the tokens a step has just produced, from the PROCESSED distribution the
+        sampler drew them from (what the reference's `logprobs` tensor is the log of): eager, after the step, one launch
+        per run of consecutive rows, one host read.
+        kind "cycle": target_probs[slot], token_ids [len(slots), k + 1] (a position without a token: any id outside the
+        vocabulary gives the dummy 0.0 / -1); "no_spec": the distribution of the last step_no_spec(); "first": that of the
+        slot's admission.  token_ids [len(slots)] for the latter two.  Returns host tensors (logprob f32, rank i32 of shape
+        [len(slots)] or [len(slots), k + 1]; top ids i32 and top logprobs f32 with a trailing [num_top])."""
+        self._check_num_top(num_top)
+        slots, V = list(slots), self.cfg.vocab_size
+        n, rps = len(slots), (self.k + 1 if kind == "cycle" else 1)
+        shape = (n, rps) if kind == "cycle" else (n,)
+        ids = torch.as_tensor(token_ids, dtype=torch.int64).reshape(n * rps).to(self.device)
+        (lp, rank, top, tlp), host, need = self._logprob_buffers(n * rps, num_top)
+        if kind == "cycle":
+            src = {b: (self.target_probs.view(-1, V), b * rps) for b in slots}
+        elif kind == "no_spec":
+            src = {b: (self.draft_probs_kbv[0], b) for b in slots}
+        elif kind == "first":
+            src = {b: (self._first_probs or {})[b] for b in slots}
+        else:
+            raise ValueError(f"kind {kind!r}: 'cycle', 'no_spec' or 'first'")
+        i = 0
+        while i < n:   # slots i .. j-1: consecutive rows of one tensor
+            t, r0 = src[slots[i]]
+            j = i + 1
+            while j < n and src[slots[j]][0].data_ptr() == t.data_ptr() and src[slots[j]][1] == r0 + (j - i) * rps:
+                j += 1
+            a, e = i * rps, j * rps
+            ops.token_logprobs_from_probs(t[r0:r0 + e - a], ids[a:e], num_top, lp[a:e], rank[a:e],
+                                          top[a * num_top:e * num_top] if num_top else None,
+                                          tlp[a * num_top:e * num_top] if num_top else None)
+            i = j
+        return self._read_logprobs(host, need, shape, num_top)
+
+    def _prompt_logits(self, hs):
+        """Raw target logits of up to PROMPT_LOGPROB_ROWS prompt rows in the ONE buffer all prompt forms share (tests wrap this
+        on the instance)."""
+        R = self.PROMPT_LOGPROB_ROWS
+        if self._plp_logits is None or self._plp_logits.shape[0] != R:
+            self._plp_logits = torch.empty(R, self.cfg.vocab_size, dtype=torch.float16, device=self.device)
+        return self.model.compute_logits(hs, SimpleNamespace(logits=self._plp_logits))
+
+    def _prompt_logprobs(self, slot: int, hs, prompt: Sequence[int], num_top: int) -> None:
+        """hs: the hidden rows 0 .. T-2 of the prompt in `slot` (row t predicts prompt[t + 1]): lm_head in chunks, logprobs
+        from the raw logits -- no temperature, penalties or constraints --, results kept for take_prompt_logprobs(slot)."""
+        rows, R = hs.shape[0], self.PROMPT_LOGPROB_ROWS
+        ids = torch.tensor(list(prompt[1:]), dtype=torch.int64, device=self.device)
+        (lp, rank, top, tlp), host, need = self._logprob_buffers(rows, num_top)
+        for a in range(0, rows, R):
+            e = min(a + R, rows)
+            ops.token_logprobs_from_logits(self._prompt_logits(hs[a:e]), ids[a:e], num_top, lp[a:e], rank[a:e],
+                                           top[a * num_top:e * num_top] if num_top else None,
+                                           tlp[a * num_top:e * num_top] if num_top else None)
+        if self._prompt_results is None:
+            self._prompt_results = {}
+        self._prompt_results[slot] = self._read_logprobs(host, need, (rows,), num_top)
+
+    def take_prompt_logprobs(self, slot: int):
+        """The prompt logprobs of the request admitted into `slot` with prompt_logprobs set -- host tensors (logprob [T-1],
+        rank [T-1], top ids [T-1, n], top logprobs [T-1, n]) for prompt tokens 1 .. T-1 -- or None; handed over once."""
+        return self._prompt_results.pop(slot, None) if self._prompt_results else None
 
     def set_sampling_params(self, slot: int, temperature: float = 0.0, top_k: int = -1, top_p: float = 1.0,
                             seed: Optional[int] = None, min_p: float = 0.0, presence_penalty: float = 0.0,

@@ -55,6 +55,7 @@ from .engine import QSpecEngine
 from .metrics import AsyncMetricsCollector, SpecDecodeWorkerMetrics
 
 VLLM_INVALID_TOKEN_ID = -1       # vllm/sequence.py:29
+MAX_LOGPROBS = 32                # QS_MAX_LOGPROBS (include/qspec_hip.h): the cap of max_logprobs with disable_logprobs=False
 
 
 # ---------------------------------------------------------------------- records (vllm/sequence.py field names)
@@ -321,6 +322,9 @@ class SpecDecodeWorker:
         self._tp_size, self._dist_init = tensor_parallel_size, distributed_init_method
         self.gpu_memory_utilization, self.swap_space_bytes = gpu_memory_utilization, swap_space_bytes
         self.max_num_batched_tokens = max_num_batched_tokens
+        if not disable_logprobs and max_logprobs > MAX_LOGPROBS:
+            raise ValueError(f"max_logprobs = {max_logprobs} with disable_logprobs=False: the logprob kernel returns at most "
+                             f"{MAX_LOGPROBS} per position")
         self.max_logprobs = max_logprobs
         self._disable_logprobs = disable_logprobs
         self._memory_probe = memory_probe
@@ -537,12 +541,35 @@ class SpecDecodeWorker:
 
     def _execute(self, req: ExecuteModelRequest, no_spec: bool, disable_all_speculation: bool,
                  num_lookahead_slots: int) -> List[SamplerOutput]:
+        self._check_requested_logprobs(req.seq_group_metadata_list or ())
         self._track_finished_requests(req)
         if not req.seq_group_metadata_list:
             return []
         if no_spec:
             return self._run_no_spec(req, skip_proposer=True)      # skip_proposer forced (:699)
         return self._run_speculative_decoding_step(req, num_lookahead_slots)
+
+    @property
+    def _real_logprobs(self) -> bool:
+        """Real logprobs are computed by the rank that returns the outputs (logits and probabilities are full-width on every
+        rank); with disable_logprobs=True -- the default -- nobody computes any and the outputs carry the dummy entries."""
+        return not self._disable_logprobs and self._rank == self._driver_rank
+
+    def _check_requested_logprobs(self, sgml) -> None:
+        """disable_logprobs=False: a request asking for more than max_logprobs is refused before anything is enqueued (the
+        dummy lists of the default never looked at the numbers)."""
+        if self._disable_logprobs:
+            return
+        for s in sgml:
+            sp = s.sampling_params
+            for name in ("logprobs", "prompt_logprobs"):
+                n = getattr(sp, name, None) if sp is not None else None
+                if n is not None and not 0 <= n <= self.max_logprobs:
+                    raise ValueError(f"request {s.request_id}: {name} = {n} outside 0..max_logprobs = {self.max_logprobs}")
+
+    @staticmethod
+    def _num_logprobs(s) -> int:
+        return (getattr(s.sampling_params, "logprobs", None) or 0) if s.sampling_params is not None else 0
 
     def _should_disable_all_speculation(self, req: ExecuteModelRequest) -> bool:
         return self.disable_by_batch_size is not None and req.running_queue_size >= self.disable_by_batch_size
@@ -563,9 +590,10 @@ class SpecDecodeWorker:
             raise NotImplementedError("beam / parallel sampling groups are not on the QSpec path (one sequence per request)")
         return next(iter(s.seq_data.items()))
 
-    def _admit(self, prompts: List[SequenceGroupMetadata]) -> List[int]:
+    def _admit(self, prompts: List[SequenceGroupMetadata], prompt_logprobs: bool = False) -> List[int]:
         """Prompts (or preempted requests coming back for recomputation) take the first free slots; their prompt pass
-        is ONE varlen forward (engine.add_sequences_to).  The engine validates every slot, prompt and block table
+        is ONE varlen forward (engine.add_sequences_to); prompt_logprobs: hand the requests' SamplingParams.prompt_logprobs
+        to it (disable_logprobs=False, on the rank that returns the outputs).  The engine validates every slot, prompt and block table
         before its first forward; should the admission still fail half-way (several prompt passes, one raising), the
         slots it had occupied are given back, so that worker and engine never disagree about which slots are free."""
         for s in prompts:
@@ -575,7 +603,7 @@ class SpecDecodeWorker:
         if len(free) < len(prompts):
             raise RuntimeError(f"no free sequence slot for request {prompts[len(free)].request_id}: "
                                f"max_num_seqs={self.max_num_seqs} are running")
-        slots, toks, tables, npts = free[:len(prompts)], [], [], []
+        slots, toks, tables, npts, plps = free[:len(prompts)], [], [], [], []
         try:
             for s, b in zip(prompts, slots):
                 seq_id, data = self._only_seq(s)
@@ -592,10 +620,13 @@ class SpecDecodeWorker:
                 # recomputation: prompt + outputs come back as one token list; penalties and min_tokens tell them apart
                 # (nothing else does: a request without them is admitted exactly as before)
                 npts.append(len(data.get_prompt_token_ids()) if lp and data.get_output_len() else None)
-            if any(n is not None for n in npts):   # (only then: an engine double need not know the keyword)
-                self.engine.add_sequences_to(slots, toks, tables, num_prompt_tokens=npts)
-            else:
-                self.engine.add_sequences_to(slots, toks, tables)
+                plps.append(getattr(sp, "prompt_logprobs", None) if prompt_logprobs and s.do_sample else None)
+            kw = {}   # (each only when needed: an engine double need not know the keywords)
+            if any(n is not None for n in npts):
+                kw["num_prompt_tokens"] = npts
+            if any(n is not None for n in plps):
+                kw["prompt_logprobs"] = plps
+            self.engine.add_sequences_to(slots, toks, tables, **kw)
         except Exception:
             for b in slots:
                 self.engine.free_slot(b)
@@ -724,21 +755,49 @@ class SpecDecodeWorker:
         sgml = req.seq_group_metadata_list
         assert req.w4a4 is False
         tokens = [VLLM_INVALID_TOKEN_ID] * len(sgml)
+        real: Dict[int, tuple] = {}            # batch index -> (rank, logprob, top ids, top logprobs) of its token
+        prompt_real: Dict[int, list] = {}      # batch index -> its prompt_logprobs list
         prompts = [i for i, s in enumerate(sgml) if s.is_prompt]
         decodes = [i for i, s in enumerate(sgml) if not s.is_prompt]
         dslots = self._decode_slots([sgml[i] for i in decodes])     # before admissions: validates the running ones
         if prompts:
-            slots = self._admit([sgml[i] for i in prompts])
+            slots = self._admit([sgml[i] for i in prompts], prompt_logprobs=self._real_logprobs)
             first = self.engine.gen_tokens[:, 0].cpu()
             self._check_out_of_cycle_errors("the prompt pass")
             for i, slot in zip(prompts, slots):
                 tokens[i] = int(first[slot])
             self.scorer_calls += 1          # one scorer call for the prompt batch, as in the reference
+            if self._real_logprobs:
+                real.update(self._token_logprobs("first", [sgml[i] for i in prompts], prompts, slots, tokens))
+                for i, slot in zip(prompts, slots):
+                    got = self.engine.take_prompt_logprobs(slot)
+                    if got is not None:
+                        prompt_real[i] = self._prompt_logprob_dicts(sgml[i], got)
         if decodes:
             tok = self._no_spec_step(dslots)
             for i, slot in zip(decodes, dslots):
                 tokens[i] = tok[slot]
-        return [self._serialize_sampler_output_no_logprobs(sgml, tokens)]
+            if self._real_logprobs:
+                real.update(self._token_logprobs("no_spec", [sgml[i] for i in decodes], decodes, dslots, tokens))
+        return [self._serialize_sampler_output_no_logprobs(sgml, tokens, real, prompt_real)]
+
+    def _token_logprobs(self, kind: str, sgs, idx: List[int], slots: List[int], tokens: List[int]) -> Dict[int, tuple]:
+        """disable_logprobs=False on the paths outside the cycle (`_run_no_spec` returns the scorer's own SamplerOutput there,
+        :710-713): batch index -> (rank, logprob, top ids, top logprobs) of the token each of `sgs` has just received, from
+        the distribution it was sampled from (engine.token_logprobs)."""
+        num_top = max([self._num_logprobs(s) for s in sgs], default=0)
+        lp, rank, top, tlp = (t.tolist() for t in self.engine.token_logprobs(kind, slots, [tokens[i] for i in idx], num_top))
+        return {i: (rank[j], lp[j], top[j][:self._num_logprobs(s)], tlp[j][:self._num_logprobs(s)])
+                for j, (i, s) in enumerate(zip(idx, sgs))}
+
+    def _prompt_logprob_dicts(self, s, got) -> List[Dict[int, Logprob]]:
+        """SamplingParams.prompt_logprobs = n: for every prompt token but the first its logprob and rank + the n best, from the
+        target's RAW logits ("Logprobs").  A recomputed request's token list also holds its outputs: the prompt's
+        rows come first."""
+        ids = self._only_seq(s)[1].get_prompt_token_ids()[1:]
+        lp, rank, top, tlp = (t[:len(ids)].tolist() for t in got)
+        return [create_logprobs_output(t, rank[j], lp[j], [v if v >= 0 else None for v in top[j]], tlp[j])
+                for j, t in enumerate(ids)]
 
     def _check_out_of_cycle_errors(self, what: str) -> None:
         """Prompt passes and non-speculative steps run outside the captured cycle (other stream, no error-word collection
@@ -755,11 +814,13 @@ class SpecDecodeWorker:
         self.engine.note_emitted([1 if b in dslots else 0 for b in range(self.max_num_seqs)])
         return {b: int(out[b]) for b in dslots}
 
-    def _serialize_sampler_output_no_logprobs(self, sgml, tokens: List[int]) -> SamplerOutput:
+    def _serialize_sampler_output_no_logprobs(self, sgml, tokens: List[int], real: Optional[Dict[int, tuple]] = None,
+                                              prompt_real: Optional[Dict[int, list]] = None) -> SamplerOutput:
         """:582-664: only the token ids are populated; a sequence group without a sample (`do_sample` False: a
-        non-terminal prompt chunk) still gets its own, empty, output."""
+        non-terminal prompt chunk) still gets its own, empty, output.  real / prompt_real (disable_logprobs=False): the
+        entries that replace the dummies, by batch index."""
         outs = []
-        for s, tok in zip(sgml, tokens):
+        for i, (s, tok) in enumerate(zip(sgml, tokens)):
             if not s.do_sample:
                 outs.append(CompletionSequenceGroupOutput(samples=[], prompt_logprobs=None))
                 continue
@@ -768,7 +829,11 @@ class SpecDecodeWorker:
             prompt_logprobs = None
             if s.is_prompt and sp is not None and sp.prompt_logprobs is not None and sp.prompt_logprobs > 0:
                 prompt_logprobs = [create_logprobs_output(t, -1, 0.0, [], []) for t in data.get_prompt_token_ids()[1:]]
-            outs.append(create_sequence_group_output(tok, -1, 0.0, seq_id, [], [], prompt_logprobs))
+            if prompt_real and i in prompt_real:
+                prompt_logprobs = prompt_real[i]
+            rank, lp, top, tlp = real[i] if real and i in real else (-1, 0.0, [], [])
+            outs.append(create_sequence_group_output(tok, rank, lp, seq_id, [v if v >= 0 else None for v in top], tlp,
+                                                     prompt_logprobs))
         return SamplerOutput(outputs=outs)
 
     def _run_speculative_decoding_step(self, req: ExecuteModelRequest, num_lookahead_slots: int) -> List[SamplerOutput]:
@@ -799,22 +864,34 @@ class SpecDecodeWorker:
         rows = [[VLLM_INVALID_TOKEN_ID] * (k + 1) for _ in sgml]
         for i in spec:
             rows[i] = out[slots[i]].tolist()
+        cycle_real = None
+        if self._real_logprobs and spec:
+            cycle_real = self.engine.token_logprobs("cycle", spec_slots, [[max(t, 0) for t in rows[i]] for i in spec],
+                                                    max(self._num_logprobs(sgml[i]) for i in spec))
+        riders = None
         if nospec:
             tok = self._no_spec_step([slots[i] for i in nospec])
             for i in nospec:
                 rows[i][0] = tok[slots[i]]
-        return self._create_output_sampler_list(sgml, rows, k, slots)
+            if self._real_logprobs:
+                riders = self._token_logprobs("no_spec", [sgml[i] for i in nospec], nospec, [slots[i] for i in nospec],
+                                              [r[0] for r in rows])
+        return self._create_output_sampler_list(sgml, rows, k, slots, spec, cycle_real, riders)
 
-    def _create_output_sampler_list(self, sgml, rows: List[List[int]], k: int, slots: List[int]) -> List[SamplerOutput]:
+    def _create_output_sampler_list(self, sgml, rows: List[List[int]], k: int, slots: List[int],
+                                    spec: Optional[List[int]] = None, cycle_real=None,
+                                    riders: Optional[Dict[int, tuple]] = None) -> List[SamplerOutput]:
         """:972-1063: [batch, k+1] accepted token ids -> one SamplerOutput per step, padded with -1 so that every
         sequence has the same number of outputs; the list stops at the first step in which no sequence emitted a token
-        (:1023-1026); metrics ride on the first one."""
+        (:1023-1026); metrics ride on the first one.  disable_logprobs=False: cycle_real = engine.token_logprobs("cycle", ...)
+        of the batch indices `spec`, riders = the step-0 entries of the requests that took the scorer-only step."""
         batch_size, num_steps = len(sgml), k + 1
         by_step = [[rows[b][j] for b in range(batch_size)] for j in range(num_steps)]
-        if self._disable_logprobs:
-            ranks, lps, topk_lps, topk_ids = self._create_dummy_logprob_lists(batch_size, num_steps, self.max_logprobs)
-        else:
-            ranks, lps, topk_lps, topk_ids = self._create_logprob_lists_from_tensors(by_step, slots, self.max_logprobs)
+        ranks, lps, topk_lps, topk_ids = self._create_dummy_logprob_lists(batch_size, num_steps, self.max_logprobs)
+        if cycle_real is not None:
+            self._fill_logprob_lists(ranks, lps, topk_lps, topk_ids, spec, cycle_real)
+        for b, (rank, lp, top, tlp) in (riders or {}).items():
+            ranks[0][b], lps[0][b], topk_ids[0][b], topk_lps[0][b] = rank, lp, [v if v >= 0 else None for v in top], tlp
         seq_ids = [self._only_seq(s)[0] for s in sgml]                                   # get_all_seq_ids_and_request_ids
         num_logprobs_per_seq = [(s.sampling_params.logprobs or 0) if s.sampling_params is not None else 0
                                 for s in sgml]                                           # get_all_num_logprobs
@@ -844,18 +921,18 @@ class SpecDecodeWorker:
         topk_ids = [[[None] * num_top_k for _ in range(batch_size)] for _ in range(num_steps)]
         return ranks, lps, topk_lps, topk_ids
 
-    def _create_logprob_lists_from_tensors(self, by_step: List[List[int]], slots: List[int], num_top_k: int):
+    @staticmethod
+    def _fill_logprob_lists(ranks, lps, topk_lps, topk_ids, spec: List[int], cycle_real) -> None:
         """:1129-1176 (`disable_logprobs=False`): log of the target's probabilities of the cycle, the accepted token's
-        logprob and rank (vllm/spec_decode/util.py:34-52) and the top-k per position.  Host-side bookkeeping with torch
-        on the engine's [B, k+1, V] target distribution -- not on the default path, not on the metric's path."""
-        probs = self.engine.target_probs[slots]                               # [batch, k+1, V]
-        logp = torch.log(probs.clamp_min(torch.finfo(torch.float32).tiny)).transpose(0, 1)   # [k+1, batch, V]
-        ids = torch.tensor(by_step, dtype=torch.int64, device=logp.device)    # [k+1, batch], -1 = nothing
-        safe = ids.clamp_min(0)
-        sel = logp.gather(-1, safe.unsqueeze(-1)).squeeze(-1)
-        ranks = (logp > sel.unsqueeze(-1)).sum(-1) + 1
-        top_lp, top_id = logp.topk(min(num_top_k, logp.shape[-1]), dim=-1)
-        return ranks.tolist(), sel.tolist(), top_lp.tolist(), top_id.tolist()
+        logprob and rank (vllm/spec_decode/util.py:34-52) and the best per position -- one kernel launch on the engine's
+        [B, k+1, V] target distribution (engine.token_logprobs; a position without a token was asked about token 0, as the
+        reference's clamp does) instead of torch passes over it; here only the lists are filled, [step][batch index]."""
+        lp, rank, top, tlp = (t.tolist() for t in cycle_real)
+        for j, b in enumerate(spec):
+            for step in range(len(ranks)):
+                ranks[step][b], lps[step][b] = rank[j][step], lp[j][step]
+                topk_ids[step][b] = [v if v >= 0 else None for v in top[j][step]]
+                topk_lps[step][b] = tlp[j][step]
 
     def _track_sequences_with_bonus_tokens(self, sgml, accepted_token_ids_by_step: List[List[int]]) -> None:
         """:1190-1210: a sequence whose last step position holds a token (!= -1) received the bonus token."""

@@ -61,7 +61,13 @@ _op("process_logits_constrained(Tensor logits, Tensor(a!) out, Tensor tok_table,
     "Tensor? draft_ids=None, int rows_per_seq=1, int j_base=0, Tensor? slot_ids=None, Tensor? active_lens=None) -> Tensor(a!)",
     ops.process_logits_constrained)
 
+# logprobs of the sampled / prompt tokens: rank, logprob and the num_top best per row, one launch
+_LOGPROBS_SCHEMA = ("(Tensor x, Tensor token_ids, int num_top, Tensor(a!) token_logprob, Tensor(b!) token_rank, "
+                    "Tensor(c!)? top_ids=None, Tensor(d!)? top_logprobs=None) -> ()")
+_op("token_logprobs_from_probs" + _LOGPROBS_SCHEMA, _none(ops.token_logprobs_from_probs))
+_op("token_logprobs_from_logits" + _LOGPROBS_SCHEMA, _none(ops.token_logprobs_from_logits))
+
 OPS = ("rms_norm_general_fuse_sum_i4", "rms_norm_general_fuse_sum_fp16", "fuse_sym_quant", "faster_fast_hadamard_transform",
        "fast_hadamard_transform", "rowwise_scaled_linear_cutlass_s4s4_unified", "w4a16_matmul", "rotary_embedding",
        "reshape_and_cache_flash", "advance_step_flashattn", "process_logits", "logit_table_set_prompt", "logit_table_catch_up",
-       "process_logits_constrained")
+       "process_logits_constrained", "token_logprobs_from_probs", "token_logprobs_from_logits")
