@@ -774,6 +774,31 @@ int qspec_ln_qkv_rope_linear_s4s4_kv8(const qspec_half* hidden_in, const qspec_h
                                       const int64_t* slot_mapping, int num_heads, int num_kv_heads, int head_size,
                                       int rot_dim, void* sync_workspace, void* stream);
 
+/* ---------------------------------------------------------------- KV block operations
+ * Whole KV-cache blocks moved on the device: copy-on-write / fork (copy) and the device half of swapping (gather, scatter).
+ * torch.ops._C_cache_ops.copy_blocks(key_caches, value_caches, block_mapping) and swap_blocks(src, dst, block_mapping),
+ *   csrc/cache_kernels.cu; called in front of every step by vllm/worker/worker.py, execute_worker (swap in, swap out, copy).
+ * A block is an opaque run of block_bytes = block_size * num_kv_heads * head_size * elem bytes (elem 2: fp16 cache, 1: e4m3
+ * cache; always a multiple of 16, which is required), so both caches use the same entries.
+ *   layer_ptrs  device array of 2 * num_layers cache base pointers (K and V of every layer, in any fixed order), each
+ *               16-byte aligned and covering every block id named; built once by the owner of the cache.
+ *   pairs       device int64 [num_pairs, 2]: (src, dst) block ids.  One src may feed several dst.  No dst may also be a
+ *               src of the same call and the dst values must be distinct: the CALLER checks this and the id range (the
+ *               Python wrapper raises ValueError before anything is enqueued); the kernel relies on it.
+ *   block_ids   device int64 [n].
+ *   staging     device memory of n records [n, 2 * num_layers, block_bytes]: record i holds block block_ids[i] of every
+ *               pointer of layer_ptrs, in its order -- a block's K and V of all layers as ONE contiguous run, the unit of
+ *               a host copy.
+ * copy:    layer[dst] = layer[src] for every pair and every pointer.   gather: staging[i] = blocks block_ids[i].
+ * scatter: blocks block_ids[i] = staging[i] (distinct ids: caller-checked).
+ * Each is ONE launch for all layers: 16-byte loads and plain vector stores, no atomics, no workspace.  A count of 0 is a
+ * no-op that enqueues nothing (the pointers may then be NULL).  Additive: the ABI version is unchanged. */
+int qspec_copy_blocks(void* const* layer_ptrs, int num_layers, const int64_t* pairs, int num_pairs, int64_t block_bytes,
+                      void* stream);
+int qspec_gather_blocks(void* const* layer_ptrs, int num_layers, const int64_t* block_ids, int n, int64_t block_bytes,
+                        void* staging, void* stream);
+int qspec_scatter_blocks(void* const* layer_ptrs, int num_layers, const int64_t* block_ids, int n, int64_t block_bytes,
+                         const void* staging, void* stream);
 
 #ifdef __cplusplus
 }

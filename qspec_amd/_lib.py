@@ -134,6 +134,9 @@ SIGNATURES = {
     "qspec_collect_error_words": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "qspec_token_logprobs_from_probs": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "qspec_token_logprobs_from_logits": (_i, [_vp, _i64, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "qspec_copy_blocks": (_i, [_vp, _i, _vp, _i, _i64, _vp]),
+    "qspec_gather_blocks": (_i, [_vp, _i, _vp, _i, _i64, _vp, _vp]),
+    "qspec_scatter_blocks": (_i, [_vp, _i, _vp, _i, _i64, _vp, _vp]),
 }
 
 # Fragment-major activation tiles (include/qspec_hip.h, "activation layout"): each of these has an `_xp` twin with the same

@@ -1200,4 +1200,36 @@ int qspec_ln_qkv_rope_linear_s4s4_kv8(const qspec_half* hidden_in, const qspec_h
                                          num_kv_heads, head_size, rot_dim, sync_workspace, stream);
 }
 
+// ---- KV block operations (cache_ops.hip)
+static int block_op_args(const char* op, const void* layer_ptrs, int num_layers, const void* ids, int n, int64_t block_bytes) {
+    if (num_layers < 1) return fail("%s: num_layers = %d < 1", op, num_layers);
+    if (n < 0) return fail("%s: negative block count", op);
+    if (block_bytes < 16 || block_bytes % 16) return fail("%s: block_bytes = %lld is not a positive multiple of 16", op, (long long)block_bytes);
+    if (n > 0 && (!layer_ptrs || !ids)) return fail("%s: a NULL pointer with %d blocks to move", op, n);
+    return 0;
+}
+int qspec_copy_blocks(void* const* layer_ptrs, int num_layers, const int64_t* pairs, int num_pairs, int64_t block_bytes,
+                      void* stream) {
+    const char* op = "qspec_copy_blocks";
+    if (int rc = block_op_args(op, layer_ptrs, num_layers, pairs, num_pairs, block_bytes)) return rc;
+    if (num_pairs == 0) return 0;
+    return finish(op, qspec::copy_blocks(layer_ptrs, num_layers, pairs, num_pairs, block_bytes, ST));
+}
+int qspec_gather_blocks(void* const* layer_ptrs, int num_layers, const int64_t* block_ids, int n, int64_t block_bytes,
+                        void* staging, void* stream) {
+    const char* op = "qspec_gather_blocks";
+    if (int rc = block_op_args(op, layer_ptrs, num_layers, block_ids, n, block_bytes)) return rc;
+    if (n == 0) return 0;
+    NONNULL(op, staging);
+    return finish(op, qspec::gather_blocks(layer_ptrs, num_layers, block_ids, n, block_bytes, staging, ST));
+}
+int qspec_scatter_blocks(void* const* layer_ptrs, int num_layers, const int64_t* block_ids, int n, int64_t block_bytes,
+                         const void* staging, void* stream) {
+    const char* op = "qspec_scatter_blocks";
+    if (int rc = block_op_args(op, layer_ptrs, num_layers, block_ids, n, block_bytes)) return rc;
+    if (n == 0) return 0;
+    NONNULL(op, staging);
+    return finish(op, qspec::scatter_blocks(layer_ptrs, num_layers, block_ids, n, block_bytes, staging, ST));
+}
+
 }  // extern "C"

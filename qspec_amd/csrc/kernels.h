@@ -271,4 +271,12 @@ int token_logprobs_from_probs(const float* probs, int64_t row_stride, const int6
                               float* token_logprob, int32_t* token_rank, int32_t* top_ids, float* top_logprobs, hipStream_t st);
 int token_logprobs_from_logits(const f16* logits, int64_t row_stride, const int64_t* token_ids, int rows, int vocab, int num_top,
                                float* token_logprob, int32_t* token_rank, int32_t* top_ids, float* top_logprobs, hipStream_t st);
+
+// cache_ops.hip: whole KV-cache blocks moved as opaque runs of block_bytes bytes (% 16 == 0) across the 2 * num_layers cache
+// tensors whose base pointers the device array layer_ptrs holds; one launch each, no workspace
+int copy_blocks(void* const* layer_ptrs, int num_layers, const int64_t* pairs, int num_pairs, int64_t block_bytes, hipStream_t st);
+int gather_blocks(void* const* layer_ptrs, int num_layers, const int64_t* block_ids, int n, int64_t block_bytes, void* staging,
+                  hipStream_t st);
+int scatter_blocks(void* const* layer_ptrs, int num_layers, const int64_t* block_ids, int n, int64_t block_bytes,
+                   const void* staging, hipStream_t st);
 }  // namespace qspec

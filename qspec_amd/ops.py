@@ -1123,3 +1123,103 @@ def collect_error_words(word_addrs, out=None, clear: bool = False):
     assert len(word_addrs) <= 4, "at most four error words per call"
     w = list(word_addrs) + [None] * (4 - len(word_addrs))
     _call("qspec_collect_error_words", w[0], w[1], w[2], w[3], 1 if clear else 0, _opt(out, "out", _I64), _stream())
+
+
+# ------------------------------------------------------------------ KV block operations (include/qspec_hip.h, "KV block operations")
+
+def validate_block_pairs(pairs, num_src: int, num_dst: int, same_space: bool = True):
+    """The (src, dst) block pairs of one copy / swap call as a list of int pairs, or ValueError -- a pure function, called
+    before anything is enqueued.  src must lie in [0, num_src), dst in [0, num_dst), the dst values must be distinct, and
+    with same_space (a copy inside one cache) no dst may also be a src of the call: the kernels rely on all of it."""
+    out = []
+    for p in pairs:
+        if len(p) != 2:
+            raise ValueError(f"block pair {p!r}: expected (src, dst)")
+        s, d = int(p[0]), int(p[1])
+        if not 0 <= s < num_src:
+            raise ValueError(f"block pair ({s}, {d}): src outside 0..{num_src - 1}")
+        if not 0 <= d < num_dst:
+            raise ValueError(f"block pair ({s}, {d}): dst outside 0..{num_dst - 1}")
+        out.append((s, d))
+    dsts = [d for _, d in out]
+    if len(set(dsts)) != len(dsts):
+        raise ValueError("a dst block appears twice in one call")
+    if same_space:
+        both = set(dsts) & set(s for s, _ in out)
+        if both:
+            raise ValueError(f"blocks {sorted(both)[:8]} are src and dst of the same call")
+    return out
+
+
+class KVBlocks:
+    """The cache tensors the block operations move blocks of: key_caches / value_caches, one [num_blocks, ...] tensor per layer,
+    all of one shape and dtype (fp16 or the byte cache).  Holds the device array of their 2 * num_layers base pointers (K0, V0,
+    K1, V1, ...: the plane order of a staging record), built ONCE here, and keeps the tensors alive."""
+
+    def __init__(self, key_caches, value_caches):
+        caches = [t for kv in zip(key_caches, value_caches) for t in kv]
+        if not caches or len(key_caches) != len(value_caches):
+            raise RuntimeError("key_caches and value_caches: one tensor per layer each")
+        first = caches[0]
+        for t in caches:
+            _chk(t, "cache", (_F16,) + _KV8)
+            if t.shape != first.shape or t.dtype != first.dtype or t.device != first.device or t.dim() < 2:
+                raise RuntimeError("the cache tensors must share one [num_blocks, ...] shape, dtype and device")
+        self.caches = caches
+        self.num_layers, self.num_blocks = len(key_caches), int(first.shape[0])
+        self.block_bytes = int(first[0].numel()) * first.element_size()
+        if self.block_bytes % 16 or any(t.data_ptr() % 16 for t in caches):
+            raise RuntimeError(f"blocks of {self.block_bytes} bytes: the block operations move 16-byte vectors")
+        self.record_bytes = 2 * self.num_layers * self.block_bytes
+        self.device = first.device
+        self.layer_ptrs = torch.tensor([t.data_ptr() for t in caches], dtype=_I64).to(self.device)
+
+    def _ids(self, ids):
+        return torch.tensor(ids, dtype=_I64).to(self.device)
+
+
+def copy_blocks(blocks: KVBlocks, pairs) -> None:
+    """torch.ops._C_cache_ops.copy_blocks (csrc/cache_kernels.cu): cache[dst] = cache[src] in every layer's K and V for the
+    (src, dst) pairs, ONE launch -- qspec_copy_blocks.  ValueError (out of range, a dst twice, a dst that is also a src) before
+    anything is enqueued; no pairs: nothing is enqueued."""
+    pairs = validate_block_pairs(pairs, blocks.num_blocks, blocks.num_blocks)
+    if not pairs:
+        return
+    dev_pairs = blocks._ids(pairs)
+    _call("qspec_copy_blocks", blocks.layer_ptrs.data_ptr(), blocks.num_layers, dev_pairs.data_ptr(), len(pairs),
+          blocks.block_bytes, _stream())
+
+
+def _staging_args(blocks: KVBlocks, block_ids, staging, distinct: bool):
+    ids = [int(b) for b in block_ids]
+    if any(not 0 <= b < blocks.num_blocks for b in ids):
+        raise ValueError(f"block id outside 0..{blocks.num_blocks - 1}")
+    if distinct and len(set(ids)) != len(ids):
+        raise ValueError("a block appears twice in one scatter")
+    if ids:
+        _chk(staging, "staging", _U8)
+        if staging.numel() < len(ids) * blocks.record_bytes or staging.data_ptr() % 16:
+            raise RuntimeError(f"staging needs {len(ids)} records of {blocks.record_bytes} bytes, 16-byte aligned")
+    return ids
+
+
+def gather_blocks(blocks: KVBlocks, block_ids, staging) -> None:
+    """The device half of a swap out: staging (uint8, [n, num_layers, 2, block_bytes]) record i = block block_ids[i] of every
+    layer's K and V, ONE launch -- qspec_gather_blocks."""
+    ids = _staging_args(blocks, block_ids, staging, distinct=False)
+    if not ids:
+        return
+    dev_ids = blocks._ids(ids)
+    _call("qspec_gather_blocks", blocks.layer_ptrs.data_ptr(), blocks.num_layers, dev_ids.data_ptr(), len(ids),
+          blocks.block_bytes, staging.data_ptr(), _stream())
+
+
+def scatter_blocks(blocks: KVBlocks, block_ids, staging) -> None:
+    """The device half of a swap in: block block_ids[i] of every layer's K and V = staging record i (distinct ids), ONE launch
+    -- qspec_scatter_blocks."""
+    ids = _staging_args(blocks, block_ids, staging, distinct=True)
+    if not ids:
+        return
+    dev_ids = blocks._ids(ids)
+    _call("qspec_scatter_blocks", blocks.layer_ptrs.data_ptr(), blocks.num_layers, dev_ids.data_ptr(), len(ids),
+          blocks.block_bytes, staging.data_ptr(), _stream())

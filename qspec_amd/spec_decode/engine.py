@@ -64,11 +64,12 @@ class QSpecEngine:
     def __init__(self, model: QuarotLlamaForCausalLM, num_speculative_tokens: int = 3, max_batch: int = 4,
                  max_model_len: int = 1024, block_size: int = 16, max_new_tokens: int = 1024, use_graph: bool = True,
                  seed: int = 0, num_blocks: Optional[int] = None, acceptance_sampler=None, kv_cache_dtype: str = "auto",
-                 kv_scales=None):
+                 kv_scales=None, num_cpu_blocks: int = 0):
         """kv_cache_dtype: "auto" (fp16 cache) or "fp8" / "fp8_e4m3" (one e4m3 byte per element, half the cache bytes;
         include/qspec_hip.h, "FP8 KV cache").  kv_scales: per layer (k_scale, v_scale) for the fp8 cache, kept on THIS engine
         and handed to every forward (the model, which other engines may share, is not touched); None keeps the model's
-        (read from the checkpoint) or 1.0."""
+        (read from the checkpoint) or 1.0.  num_cpu_blocks: blocks of the pinned host cache swap_out / swap_in move KV blocks to
+        and from (initialize_cache's second number); 0 allocates nothing."""
         if kv_cache_dtype not in ("auto", "fp8", "fp8_e4m3"):
             raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}: 'auto', 'fp8' or 'fp8_e4m3'")
         self.kv_cache_dtype = "auto" if kv_cache_dtype == "auto" else "fp8"
@@ -106,6 +107,11 @@ class QSpecEngine:
         self._kv_fw = {} if kv_scales is None else {"kv_scales": kv_scales}   # forward() keywords; empty unless fp8 + own scales
         self.kv_caches = [(torch.zeros(shape, dtype=kv_dtype, device=dev),
                            torch.zeros(shape, dtype=kv_dtype, device=dev)) for _ in range(cfg.num_hidden_layers)]
+        # ---- the swap space: one pinned record (K and V of every layer) per CPU block, made only when asked for
+        if int(num_cpu_blocks) < 0:
+            raise ValueError("num_cpu_blocks < 0")
+        if int(num_cpu_blocks):
+            self.allocate_cpu_cache(int(num_cpu_blocks))
         if self.num_blocks >= B * self.blocks_per_seq:
             self.block_tables = torch.arange(B * self.blocks_per_seq, dtype=i32, device=dev).view(B, self.blocks_per_seq).contiguous()
             self._capacity = [self.blocks_per_seq * block_size] * B    # tokens the slot's block table covers (host)
@@ -199,6 +205,12 @@ class QSpecEngine:
     _plp_logits: Optional[torch.Tensor] = None
     _lp_dev: Optional[torch.Tensor] = None    # one int32 device buffer for a call's four outputs, and its pinned host twin
     _lp_host: Optional[torch.Tensor] = None
+    # block operations (copy_blocks / swap_out / swap_in): everything below stays None until one is asked for
+    num_cpu_blocks = 0
+    cpu_cache: Optional[torch.Tensor] = None       # pinned uint8 [num_cpu_blocks, record_bytes]
+    _kv_blocks = None                              # ops.KVBlocks: the device array of the 2 x layers cache base pointers
+    _swap_staging: Optional[torch.Tensor] = None   # device uint8 [largest call so far, record_bytes]
+    SAMPLE_SEED_STRIDE = 0x9E3779B97F4A7C15        # sample i of a seeded group draws with (seed + i * this) mod 2^64
 
     # ------------------------------------------------------------------ prefill (_run_no_spec, :666-720)
     @torch.no_grad()
@@ -212,21 +224,23 @@ class QSpecEngine:
     def add_sequences_to(self, slots: Sequence[int], prompts: Sequence[Sequence[int]],
                          block_tables: Optional[Sequence[Optional[Sequence[int]]]] = None,
                          num_prompt_tokens: Optional[Sequence[Optional[int]]] = None,
-                         prompt_logprobs: Optional[Sequence[Optional[int]]] = None) -> None:
+                         prompt_logprobs: Optional[Sequence[Optional[int]]] = None,
+                         sample_slots: Optional[Sequence[Optional[Sequence[int]]]] = None) -> None:
         """Admit several requests at once: one W4A16 forward over the concatenated prompts (flash-attn varlen form).
         num_prompt_tokens[i] (None: all of it): how many tokens of prompts[i] are the request's PROMPT -- a preempted
         request comes back with prompt + outputs as one token list, and the penalties / min_tokens tell the two apart.
         prompt_logprobs[i] (None: not asked for): SamplingParams.prompt_logprobs of request i -- the logprob and rank of every
         token of prompts[i] but the first plus that many best, from the RAW target logits; take_prompt_logprobs(slot) hands
-        them over."""
+        them over.  sample_slots[i] (None: none): further EMPTY slots that receive additional first-token samples of prompts[i]
+        (SamplingParams.n / best_of > 1) -- see add_sequence."""
         cfg, dev = self.cfg, self.device
         n = len(slots)
         if n == 0:
             return
+        extra = [()] * n if sample_slots is None else [tuple(int(c) for c in (e or ())) for e in sample_slots]
+        self._check_sample_slots(list(slots) + [c for e in extra for c in e])
         # Validate EVERY slot, prompt and block table before the first forward: a later request that does not fit must
         # not leave earlier ones of the same call admitted (their slots would be occupied here and free in the worker).
-        if len(set(slots)) != n:
-            raise ValueError("a slot appears twice in one admission")
         for i, b in enumerate(slots):
             if not 0 <= b < self.B or self._len_ub[b] != 0:
                 raise ValueError(f"slot {b} is not an empty slot of this engine")
@@ -247,7 +261,7 @@ class QSpecEngine:
             self._check_num_top(v)
         if n == 1:
             self.add_sequence(slots[0], prompts[0], None if block_tables is None else block_tables[0],
-                              num_prompt_tokens=npts[0], prompt_logprobs=plps[0])
+                              num_prompt_tokens=npts[0], prompt_logprobs=plps[0], **({"sample_slots": extra[0]} if extra[0] else {}))
             return
         if sum(len(p) for p in prompts) > self.PREFILL_TOKEN_BUDGET:
             # several passes of at most PREFILL_TOKEN_BUDGET tokens (measured: 4 x 512 tokens in one pass 37 ms vs 49 ms
@@ -257,7 +271,7 @@ class QSpecEngine:
                 if i == n or (group and tokens + len(prompts[i]) > self.PREFILL_TOKEN_BUDGET):
                     self.add_sequences_to([slots[j] for j in group], [prompts[j] for j in group],
                                           None if block_tables is None else [block_tables[j] for j in group],
-                                          [npts[j] for j in group], [plps[j] for j in group])
+                                          [npts[j] for j in group], [plps[j] for j in group], [extra[j] for j in group])
                     group, tokens = [], 0
                 if i < n:
                     group.append(i)
@@ -277,9 +291,15 @@ class QSpecEngine:
                                torch.tensor(lens, dtype=torch.int32, device=dev), q_start, Tmax, 1)
         hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False, **self._kv_fw)
         last = (q_start[1:].long() - 1)
+        rows, row_slots, row_lens = [], [], []      # one first-token row per request and per additional sample of it
         for i, b in enumerate(slots):
             self.sampling.admit_tokens(b, prompts[i], npts[i])
-        self._first_token(hs[last].contiguous(), s, list(slots), lens)
+            self._admit_samples(b, extra[i], prompts[i], npts[i])
+            rows += [i] * (1 + len(extra[i]))
+            row_slots += [b, *extra[i]]
+            row_lens += [lens[i]] * (1 + len(extra[i]))
+        first_hs = hs[last] if len(rows) == n else hs[last][torch.tensor(rows, dtype=torch.int64, device=dev)]
+        self._first_token(first_hs.contiguous(), s, row_slots, row_lens)
         starts = q_start.tolist() if any(v is not None for v in plps) else None
         for i, b in enumerate(slots):
             if plps[i] is not None:
@@ -288,15 +308,24 @@ class QSpecEngine:
 
     @torch.no_grad()
     def add_sequence(self, slot: int, prompt: Sequence[int], block_table: Optional[Sequence[int]] = None,
-                     sync: bool = True, num_prompt_tokens: Optional[int] = None, prompt_logprobs: Optional[int] = None) -> None:
+                     sync: bool = True, num_prompt_tokens: Optional[int] = None, prompt_logprobs: Optional[int] = None,
+                     sample_slots: Sequence[int] = ()) -> None:
         """Admit a request into an empty slot: scorer-only W4A16 prompt pass (the proposer never runs on prefill,
         spec_decode_worker.py:699); the first generated token is the target's greedy token.  prompt_logprobs: see
-        add_sequences_to."""
+        add_sequences_to.
+        sample_slots (SamplingParams.n / best_of > 1): further EMPTY slots that each receive one more first-token sample of the
+        same prompt.  The prompt pass runs ONCE; the first token is sampled over the prompt's last hidden row repeated once per
+        sample.  Every sample slot gets the parent's block table (the prompt's blocks are shared until the scheduler hands a
+        sample its own copy: copy_blocks + set_block_table), the prompt in its token table, the parent's sampling parameters and
+        its own first token; sample i (the parent is 0) of a seeded request draws with seed (seed + i * SAMPLE_SEED_STRIDE)
+        mod 2^64, unseeded samples with the engine stream (row-indexed: the rows differ)."""
         cfg, dev, b = self.cfg, self.device, slot
         if not 0 <= b < self.B:
             raise ValueError(f"slot {b} outside the captured batch of {self.B}")
         if self._len_ub[b] != 0:
             raise ValueError(f"slot {b} is occupied; free_slot() it first")
+        sample_slots = [int(c) for c in sample_slots]
+        self._check_sample_slots([b] + sample_slots)
         if num_prompt_tokens is not None and not 1 <= num_prompt_tokens <= len(prompt):
             raise ValueError(f"num_prompt_tokens {num_prompt_tokens} outside 1..{len(prompt)}")
         self._check_num_top(prompt_logprobs)
@@ -317,17 +346,42 @@ class QSpecEngine:
                                torch.tensor([0, T], dtype=torch.int32, device=dev), T, n_splits_for(T))
         hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False, **self._kv_fw)
         self.sampling.admit_tokens(b, prompt, num_prompt_tokens)
-        self._first_token(hs[T - 1:T], s, [b], [T])
+        self._admit_samples(b, sample_slots, prompt, num_prompt_tokens)
+        m = 1 + len(sample_slots)
+        self._first_token(hs[T - 1:T] if m == 1 else hs[T - 1:T].expand(m, -1).contiguous(), s, [b] + sample_slots, [T] * m)
         if prompt_logprobs is not None:
             self._prompt_logprobs(b, hs[:T - 1], prompt, prompt_logprobs)
         if sync:
             torch.cuda.synchronize()
+
+    def _check_sample_slots(self, slots: List[int]) -> None:
+        """Every slot of one admission, sample slots included: distinct, inside the batch, empty."""
+        if len(set(slots)) != len(slots):
+            raise ValueError("a slot appears twice in one admission")
+        for c in slots:
+            if not 0 <= c < self.B or self._len_ub[c] != 0:
+                raise ValueError(f"slot {c} is not an empty slot of this engine")
+
+    def _admit_samples(self, parent: int, sample_slots: Sequence[int], prompt: Sequence[int], num_prompt_tokens: Optional[int]) -> None:
+        """What a sample slot shares with its parent, in front of the first token: block table, sampling parameters (seed
+        derived), token-table row of the prompt."""
+        for i, c in enumerate(sample_slots, 1):
+            if self._bt_host[parent] is not None:
+                self.set_block_table(c, self._bt_host[parent])
+            elif self._bt_host[c] is not None or self.num_blocks >= self.B * self.blocks_per_seq:
+                # contiguous mode: the parent's default range (recorded as a brought table: free_slot restores the slot's own)
+                lo = parent * self.blocks_per_seq
+                self.set_block_table(c, list(range(lo, lo + self.blocks_per_seq)))
+            self.sampling.clone_params(parent, c, seed_add=i * self.SAMPLE_SEED_STRIDE)
+            self.sampling.admit_tokens(c, prompt, num_prompt_tokens)
 
     def _first_token(self, hs, scratch, slots: List[int], prompt_lens: List[int]) -> None:
         """The target's first token of freshly admitted prompts (hs: their last hidden rows): greedy, or sampled with the
         slots' parameters (a seeded request: target stream, j = 0, base position = its prompt length).  The mode comes from the
         admitted slots alone; position 0 of a request has no in-flight tokens (gen_lens of a fresh slot is 0)."""
         n, level, greedy = len(slots), self.sampling.level(slots), not self.sampling.sampling_on(slots)
+        if scratch.logits.shape[0] < n:   # additional samples of a prompt: more rows than the prompt pass's scratch has
+            scratch = SimpleNamespace(logits=torch.empty(n, self.cfg.vocab_size, dtype=torch.float16, device=self.device))
         probs = torch.empty(n, self.cfg.vocab_size, dtype=torch.float32, device=self.device)
         tok = torch.empty(n, dtype=torch.int64, device=self.device)
         rows = self.sampling.gathered_rows(slots, level, not greedy, scratch.logits[:n])
@@ -396,6 +450,94 @@ class QSpecEngine:
                 self.block_tables[slot].zero_()
                 self._capacity[slot] = 0
             self._bt_host[slot] = None
+        self.n_active = sum(1 for v in self._len_ub if v > 0)
+
+    # ------------------------------------------------------------------ block operations and forks (vllm/worker/worker.py, execute_worker)
+    def _blocks(self):
+        if self._kv_blocks is None:   # the pointer array is built once, at the first block operation
+            self._kv_blocks = ops.KVBlocks([k for k, _ in self.kv_caches], [v for _, v in self.kv_caches])
+        return self._kv_blocks
+
+    def allocate_cpu_cache(self, num_cpu_blocks: int) -> None:
+        """The swap space (the constructor's num_cpu_blocks; the worker's initialize_cache calls this): ONE pinned uint8
+        [num_cpu_blocks, record_bytes] tensor, a record = K and V of one block over all layers."""
+        if num_cpu_blocks < 1:
+            raise ValueError("the CPU cache needs at least one block")
+        k0 = self.kv_caches[0][0]
+        record = 2 * len(self.kv_caches) * k0[0].numel() * k0.element_size()
+        self.cpu_cache = torch.empty(num_cpu_blocks, record, dtype=torch.uint8, pin_memory=(self.device.type == "cuda"))
+        self.num_cpu_blocks = num_cpu_blocks
+
+    def _staging(self, n: int) -> torch.Tensor:
+        blocks = self._blocks()
+        if self._swap_staging is None or self._swap_staging.shape[0] < n:   # sized to the largest call so far
+            self._swap_staging = torch.empty(n, blocks.record_bytes, dtype=torch.uint8, device=self.device)
+        return self._swap_staging
+
+    def _swap_pairs(self, pairs, gpu_first: bool):
+        if self.cpu_cache is None:
+            if not list(pairs):
+                return []
+            raise ValueError("this engine has no CPU cache (num_cpu_blocks = 0)")
+        n_src, n_dst = (self.num_blocks, self.num_cpu_blocks) if gpu_first else (self.num_cpu_blocks, self.num_blocks)
+        return ops.validate_block_pairs(pairs, n_src, n_dst, same_space=False)
+
+    @torch.no_grad()
+    def copy_blocks(self, pairs) -> None:
+        """blocks_to_copy: cache[dst] = cache[src] for the (src, dst) block pairs in every layer's K and V -- one launch on the
+        current stream, outside every captured graph (copy-on-write, forks).  One src may feed several dst; ValueError, nothing
+        enqueued: an id outside the cache, a dst twice, a dst that is also a src of the call."""
+        pairs = ops.validate_block_pairs(pairs, self.num_blocks, self.num_blocks)
+        if pairs:
+            ops.copy_blocks(self._blocks(), pairs)
+
+    @torch.no_grad()
+    def swap_out(self, pairs) -> None:
+        """blocks_to_swap_out: (gpu block, cpu block) pairs.  ONE gather launch packs the blocks into contiguous records (K and V
+        of every layer), then one asynchronous record-sized copy per block lands them in the pinned CPU cache; all on the
+        current stream, so a later swap_in or cycle is ordered behind it.  ValueError with nothing enqueued on a bad pair."""
+        pairs = self._swap_pairs(pairs, gpu_first=True)
+        if not pairs:
+            return
+        stage = self._staging(len(pairs))
+        ops.gather_blocks(self._blocks(), [g for g, _ in pairs], stage)
+        for i, (_, c) in enumerate(pairs):
+            self.cpu_cache[c].copy_(stage[i], non_blocking=True)
+
+    @torch.no_grad()
+    def swap_in(self, pairs) -> None:
+        """blocks_to_swap_in: (cpu block, gpu block) pairs: the record copies first, then ONE scatter launch."""
+        pairs = self._swap_pairs(pairs, gpu_first=False)
+        if not pairs:
+            return
+        stage = self._staging(len(pairs))
+        for i, (c, _) in enumerate(pairs):
+            stage[i].copy_(self.cpu_cache[c], non_blocking=True)
+        ops.scatter_blocks(self._blocks(), [g for _, g in pairs], stage)
+
+    @torch.no_grad()
+    def fork_slot(self, src: int, dst: int, block_table: Optional[Sequence[int]] = None) -> None:
+        """The sequence in the occupied slot `src` continues in the empty slot `dst` as well (a scheduler forking mid-generation):
+        every per-slot piece of state is copied -- lengths, last token, generated tokens, host bounds, the SlotSampling state
+        (parameters, seed, token-table row, constraint rows and tail).  block_table: the fork's own table (shared blocks plus
+        its copy of the last, partially filled one: copy_blocks first); None: the parent's."""
+        for b, want in ((src, True), (dst, False)):
+            if not 0 <= b < self.B or (self._len_ub[b] > 0) != want:
+                raise ValueError(f"slot {b} is not {'an occupied' if want else 'an empty'} slot of this engine")
+        if block_table is None:
+            block_table = self._bt_host[src]
+            if block_table is None:
+                lo = src * self.blocks_per_seq
+                block_table = list(range(lo, lo + self.blocks_per_seq))
+        self._validate_block_table([int(b) for b in block_table])
+        self.sync_lens()   # exact bounds: the fork starts from what the parent really holds
+        self.set_block_table(dst, block_table)
+        self.sampling.fork(src, dst)
+        for t in (self.seq_lens, self.gen_lens, self.last_token, self.gen_tokens):
+            t[dst].copy_(t[src])
+        self._len_ub[dst], self._gen_ub[dst] = self._len_ub[src], self._gen_ub[src]
+        if self._first_probs and src in self._first_probs:
+            self._first_probs[dst] = self._first_probs[src]
         self.n_active = sum(1 for v in self._len_ub if v > 0)
 
     # ------------------------------------------------------------------ logprobs (sampler.py:284, :861-879, :882 ff.)

@@ -159,6 +159,32 @@ class SlotSampling:
         self.v_samp_topp[slot * k1:(slot + 1) * k1] = want[2]
         self._samp_host[slot] = want
 
+    def clone_params(self, src: int, dst: int, seed_add: int = 0, occupied: bool = False) -> None:
+        """The parameters of slot `src` set on slot `dst` (an additional sample of a request, a fork): the same values through
+        set(), so the same canonical forms and the same uploads-only-on-change; a seeded request's seed becomes
+        (seed + seed_add) mod 2^64."""
+        temp, topk, topp = self._samp_host[src]
+        seed = self._seed_host[src]
+        min_p, pres, freq, rep, min_tokens, stop = self._lp(src)
+        bias, allowed, words = self._tc(src) or ((), None, ())
+        self.set(dst, temp, topk, topp, None if seed is None else (seed + seed_add) % (1 << 64), min_p, pres, freq, rep, min_tokens,
+                 stop, dict(bias), allowed, [list(w) for w in words], occupied=occupied)
+
+    def fork(self, src: int, dst: int) -> None:
+        """Everything slot `src` holds here copied to the EMPTY slot `dst`: the parameters (same seed: a fork continues its
+        parent's draws until the two diverge), the token-table row with counted_len and the output base, the pre-admission
+        tail of the token constraints.  Plain copies: forking is not on the step's critical path."""
+        self.clone_params(src, dst)
+        if self._lp_host is None:
+            return
+        self.tok_table[dst].copy_(self.tok_table[src])
+        self.counted_len[dst] = self.counted_len[src]
+        self.lp_gen_base[dst] = self.lp_gen_base[src]
+        self._gen_base_host[dst] = self._gen_base_host[src]
+        if self.tc is not None:
+            self.tc.tail[dst].copy_(self.tc.tail[src])
+            self.tc.meta[dst, 3] = self.tc.meta[src, 3]
+
     def _validate_constraints(self, slot: int, logit_bias, allowed_token_ids, bad_words_token_ids, stop: Sequence[int],
                               occupied: bool):
         """The canonical form of a request's token constraints -- (sorted (id, bias) pairs, sorted allowed ids or None, bad

@@ -32,7 +32,8 @@ The decisions the reference inherits from `attn_backend.get_name() == "FLASH_ATT
 loop; :214-235, draft_model_runner.py:154) are owned here: both are always on.
 
 Batch membership follows `seq_group_metadata_list` on EVERY call: requests are identified by `request_id`, keep their
-engine slot until `finished_requests_ids` names them, may be scheduled in any order and in any subset (sequences that
+engine slot -- one per sequence id: a group sampling n / best_of > 1 sequences holds that many -- until
+`finished_requests_ids` names them, may be scheduled in any order and in any subset (sequences that
 sit out a step do not advance), and new prompts are admitted whenever a slot is free.  The scheduler's block tables
 (`SequenceGroupMetadata.block_tables`) are honoured when given.
 
@@ -87,6 +88,10 @@ class SamplingParams:
     allowed_token_ids: Optional[List[int]] = None
     bad_words_token_ids: Optional[List[List[int]]] = None
     logits_processors: Optional[List[Any]] = None
+    # parallel sampling: best_of (default: n) sequences are sampled from one prompt pass; beam search is refused
+    n: int = 1
+    best_of: Optional[int] = None
+    use_beam_search: bool = False
 
 
 @dataclass
@@ -126,13 +131,20 @@ class ExecuteModelRequest:
     running_queue_size: int = 0
     finished_requests_ids: List[str] = field(default_factory=list)   # vllm/sequence.py:1295
     w4a4: bool = False                                   # vllm/sequence.py:1301
+    # block moves in front of the step (vllm/sequence.py; vllm/worker/worker.py, execute_worker): (cpu, gpu), (gpu, cpu), (src, dst)
+    blocks_to_swap_in: List[Tuple[int, int]] = field(default_factory=list)
+    blocks_to_swap_out: List[Tuple[int, int]] = field(default_factory=list)
+    blocks_to_copy: List[Tuple[int, int]] = field(default_factory=list)
 
     def clone(self, seq_group_metadata_list):
         """vllm/sequence.py:1331-1348: every field except `w4a4` is carried over."""
         return ExecuteModelRequest(seq_group_metadata_list=seq_group_metadata_list,
                                    num_lookahead_slots=self.num_lookahead_slots,
                                    running_queue_size=self.running_queue_size,
-                                   finished_requests_ids=self.finished_requests_ids)
+                                   finished_requests_ids=self.finished_requests_ids,
+                                   blocks_to_swap_in=list(self.blocks_to_swap_in),
+                                   blocks_to_swap_out=list(self.blocks_to_swap_out),
+                                   blocks_to_copy=list(self.blocks_to_copy))
 
 
 @dataclass
@@ -191,6 +203,16 @@ class SpeculativeConfig:
     typical_acceptance_sampler_posterior_alpha: float = 0.3
     disable_logprobs: bool = True        # vllm/config.py:1788-1789: logprobs are off during speculation by default
     disable_log_stats: bool = False
+
+
+@dataclass
+class _SampleGroup:
+    """A request sampling several sequences from one prompt: its engine slots (the parent's first, then the samples' in
+    sample order), the first token of each, and which sequence id sits in which slot.  The samples' sequence ids are the
+    scheduler's to choose: they are bound when the group first comes back with them."""
+    slots: List[int]
+    first: List[int] = field(default_factory=list)
+    bound: Dict[int, int] = field(default_factory=dict)
 
 
 class DeviceHandoffTimeout(RuntimeError):
@@ -457,7 +479,9 @@ class SpecDecodeWorker:
 
     def initialize_cache(self, num_gpu_blocks: int, num_cpu_blocks: int) -> None:
         """:428-444 + vllm/worker/worker.py:290-327 (raise_if_cache_size_invalid, ref_initilize_cache): one cache
-        engine of `num_gpu_blocks` blocks for both passes."""
+        engine of `num_gpu_blocks` blocks for both passes, and -- only when num_cpu_blocks > 0, through a call of its own behind
+        the constructor, so that an engine (or a test double) that predates swapping is built and used exactly as before -- its
+        swap space of `num_cpu_blocks` pinned blocks (QSpecEngine.allocate_cpu_cache)."""
         if num_gpu_blocks <= 0:
             raise ValueError("No available memory for the cache blocks. Try increasing `gpu_memory_utilization` when "
                              "initializing the engine.")
@@ -468,6 +492,8 @@ class SpecDecodeWorker:
         self.engine = self._engine_factory(self._model, self.speculative_config.num_speculative_tokens,
                                            self.max_num_seqs, self.max_model_len, self.block_size, seed=self._seed,
                                            num_blocks=num_gpu_blocks, **self._sampler_kwargs(), **self._kv_kwargs())
+        if num_cpu_blocks and num_cpu_blocks > 0 and hasattr(self.engine, "allocate_cpu_cache"):
+            self.engine.allocate_cpu_cache(int(num_cpu_blocks))
         self._metrics = AsyncMetricsCollector(self.engine.sampler)
         self._metrics.init_gpu_tensors(self._rank)
 
@@ -542,12 +568,21 @@ class SpecDecodeWorker:
     def _execute(self, req: ExecuteModelRequest, no_spec: bool, disable_all_speculation: bool,
                  num_lookahead_slots: int) -> List[SamplerOutput]:
         self._check_requested_logprobs(req.seq_group_metadata_list or ())
+        self._apply_block_operations(req)
         self._track_finished_requests(req)
         if not req.seq_group_metadata_list:
             return []
         if no_spec:
             return self._run_no_spec(req, skip_proposer=True)      # skip_proposer forced (:699)
         return self._run_speculative_decoding_step(req, num_lookahead_slots)
+
+    def _apply_block_operations(self, req) -> None:
+        """vllm/worker/worker.py, execute_worker: swap in, swap out, copy -- in that order, in front of everything else of the
+        step, on every rank (the lists arrive with the broadcast request).  The engine is called only for a non-empty list."""
+        for name, method in (("blocks_to_swap_in", "swap_in"), ("blocks_to_swap_out", "swap_out"), ("blocks_to_copy", "copy_blocks")):
+            pairs = getattr(req, name, None)
+            if pairs:
+                getattr(self.engine, method)([(int(a), int(b)) for a, b in pairs])
 
     @property
     def _real_logprobs(self) -> bool:
@@ -580,15 +615,95 @@ class SpecDecodeWorker:
             for seq_id in self._request_id_seq_id_mapping.get(rid, ()):
                 self._seq_with_bonus_token_in_last_step.discard(seq_id)
             self._request_id_seq_id_mapping.pop(rid, None)
-            slot = self._slots.pop(rid, None)
-            if slot is not None:
-                self.engine.free_slot(slot)
+            self._release(rid)
+
+    # ---- slots: one per sequence id.  self._slots: request id -> the slot of its first (for most requests: only) sequence;
+    # self._groups: request id -> _SampleGroup, for the requests that hold more than one slot
+    _groups: Optional[Dict[str, _SampleGroup]] = None
+
+    def _group(self, rid: str) -> Optional[_SampleGroup]:
+        return self._groups.get(rid) if self._groups else None
+
+    def _release(self, rid: str) -> None:
+        """The request leaves (finished, aborted, or about to be recomputed): ALL of its slots go back to the engine."""
+        slot = self._slots.pop(rid, None)
+        group = self._groups.pop(rid, None) if self._groups else None
+        for b in (group.slots if group is not None else [] if slot is None else [slot]):
+            self.engine.free_slot(b)
+
+    def _taken_slots(self) -> Set[int]:
+        return set(self._slots.values()).union(*(g.slots for g in (self._groups or {}).values()))
 
     @staticmethod
     def _only_seq(s: SequenceGroupMetadata) -> Tuple[int, SequenceData]:
         if len(s.seq_data) != 1:
-            raise NotImplementedError("beam / parallel sampling groups are not on the QSpec path (one sequence per request)")
+            raise NotImplementedError("a prompt or a batch row carries exactly one sequence (beam search is not on the QSpec path)")
         return next(iter(s.seq_data.items()))
+
+    @staticmethod
+    def _num_samples(s: SequenceGroupMetadata) -> int:
+        """Sequences a PROMPT starts: SamplingParams.best_of (default: n).  A request that comes back for recomputation with
+        outputs already has its sequences: one.  Beam search is refused."""
+        sp = s.sampling_params
+        if sp is not None and getattr(sp, "use_beam_search", False):
+            raise NotImplementedError("beam search (use_beam_search) is not on the QSpec path")
+        _, data = SpecDecodeWorker._only_seq(s)
+        if sp is None or data.get_output_len():
+            return 1
+        return max(1, int(getattr(sp, "best_of", None) or getattr(sp, "n", 1) or 1))
+
+    def _sequence_rows(self, sgml) -> Tuple[list, Optional[List[int]]]:
+        """One batch row per SEQUENCE: (rows, owner).  A group that arrives with several sequence ids (the samples of an
+        n / best_of > 1 request, from their second step on) becomes one single-sequence row each, in its seq_data order;
+        owner[r] = the index of row r's group in sgml.  Every group single-sequence: (sgml itself, None)."""
+        if all(len(s.seq_data) == 1 for s in sgml):
+            return sgml, None
+        rows, owner = [], []
+        for i, s in enumerate(sgml):
+            if len(s.seq_data) == 1:
+                rows.append(s)
+                owner.append(i)
+                continue
+            if s.is_prompt:
+                self._only_seq(s)   # raises
+            sp = s.sampling_params
+            if sp is not None and getattr(sp, "use_beam_search", False):
+                raise NotImplementedError("beam search (use_beam_search) is not on the QSpec path")
+            self._bind_samples(s)
+            for seq_id, data in s.seq_data.items():
+                tables = getattr(s, "block_tables", None)
+                rows.append(SequenceGroupMetadata(
+                    s.request_id, False, {seq_id: data}, getattr(s, "num_speculative_tokens", None),
+                    {seq_id: tables[seq_id]} if tables and tables.get(seq_id) is not None else None, sp,
+                    getattr(s, "do_sample", True), getattr(s, "token_chunk_size", None)))
+                owner.append(i)
+        return rows, owner
+
+    def _bind_samples(self, s) -> None:
+        """The scheduler names the samples of a group on their second step.  Each unknown sequence id (ascending) takes the
+        reserved sample slot (ascending sample index) whose first token is that sequence's last output token; samples with
+        equal first tokens are interchangeable up to their seed."""
+        group = self._group(s.request_id)
+        if group is None:
+            if s.request_id not in self._slots:
+                raise KeyError(f"request {s.request_id} was never prefilled on this worker (or has finished)")
+            raise ValueError(f"request {s.request_id} arrives with {len(s.seq_data)} sequences but was admitted with one")
+        for seq_id in sorted(q for q in s.seq_data if q not in group.bound):
+            toks = s.seq_data[seq_id].get_token_ids()
+            taken = set(group.bound.values())
+            slot = next((b for b, t in zip(group.slots, group.first) if b not in taken and toks and t == toks[-1]), None)
+            if slot is None:
+                raise ValueError(f"request {s.request_id}: sequence {seq_id} ends in a token none of the group's unbound samples "
+                                 "produced")
+            group.bound[seq_id] = slot
+
+    def _slot_of(self, rid: str, seq_id: int) -> int:
+        group = self._group(rid)
+        if group is not None:
+            if seq_id not in group.bound:
+                raise KeyError(f"request {rid}: sequence {seq_id} is not one of the group's sequences")
+            return group.bound[seq_id]
+        return self._slots[rid]
 
     def _admit(self, prompts: List[SequenceGroupMetadata], prompt_logprobs: bool = False) -> List[int]:
         """Prompts (or preempted requests coming back for recomputation) take the first free slots; their prompt pass
@@ -596,14 +711,22 @@ class SpecDecodeWorker:
         to it (disable_logprobs=False, on the rank that returns the outputs).  The engine validates every slot, prompt and block table
         before its first forward; should the admission still fail half-way (several prompt passes, one raising), the
         slots it had occupied are given back, so that worker and engine never disagree about which slots are free."""
+        counts = [self._num_samples(s) for s in prompts]   # (a request sampling m sequences takes m slots)
         for s in prompts:
             if s.request_id in self._slots:          # recomputation: start over
-                self.engine.free_slot(self._slots.pop(s.request_id))
-        free = [b for b in range(self.max_num_seqs) if b not in self._slots.values()]
-        if len(free) < len(prompts):
-            raise RuntimeError(f"no free sequence slot for request {prompts[len(free)].request_id}: "
+                self._release(s.request_id)
+        taken = self._taken_slots()
+        free = [b for b in range(self.max_num_seqs) if b not in taken]
+        if len(free) < sum(counts):
+            short = next(i for i in range(len(prompts)) if sum(counts[:i + 1]) > len(free))
+            raise RuntimeError(f"no free sequence slot for request {prompts[short].request_id}: "
                                f"max_num_seqs={self.max_num_seqs} are running")
-        slots, toks, tables, npts, plps = free[:len(prompts)], [], [], [], []
+        it = iter(free)
+        slots, samples = [], []
+        for m in counts:                             # the request's own slot, then those of its additional samples
+            slots.append(next(it))
+            samples.append([next(it) for _ in range(m - 1)])
+        toks, tables, npts, plps = [], [], [], []
         try:
             for s, b in zip(prompts, slots):
                 seq_id, data = self._only_seq(s)
@@ -626,14 +749,21 @@ class SpecDecodeWorker:
                 kw["num_prompt_tokens"] = npts
             if any(n is not None for n in plps):
                 kw["prompt_logprobs"] = plps
+            if any(samples):
+                kw["sample_slots"] = samples
             self.engine.add_sequences_to(slots, toks, tables, **kw)
         except Exception:
-            for b in slots:
+            for b in slots + [c for extra in samples for c in extra]:
                 self.engine.free_slot(b)
             raise
-        for s, slot in zip(prompts, slots):
+        for s, slot, extra in zip(prompts, slots, samples):
             self._slots[s.request_id] = slot
-            self._request_id_seq_id_mapping[s.request_id].add(self._only_seq(s)[0])
+            seq_id = self._only_seq(s)[0]
+            self._request_id_seq_id_mapping[s.request_id].add(seq_id)
+            if extra:
+                if self._groups is None:
+                    self._groups = {}
+                self._groups[s.request_id] = _SampleGroup(slots=[slot] + extra, bound={seq_id: slot})
         return slots
 
     @staticmethod
@@ -723,8 +853,8 @@ class SpecDecodeWorker:
         for s in sgml:
             if s.request_id not in self._slots:
                 raise KeyError(f"request {s.request_id} was never prefilled on this worker (or has finished)")
-            slot = self._slots[s.request_id]
             seq_id, data = self._only_seq(s)
+            slot = self._slot_of(s.request_id, seq_id)
             if s.block_tables and s.block_tables.get(seq_id) is not None:
                 self.engine.set_block_table(slot, s.block_tables[seq_id])
             if data.output_token_ids and data.get_len() != self.engine._len_ub[slot]:
@@ -732,7 +862,7 @@ class SpecDecodeWorker:
                                  f"{self.engine._len_ub[slot]}: outputs were dropped or re-ordered between steps")
             slots.append(slot)
         if len(set(slots)) != len(slots):
-            raise ValueError("a request appears twice in seq_group_metadata_list")
+            raise ValueError("a request (or a sequence of it) appears twice in seq_group_metadata_list")
         return slots
 
     def _read_cycle(self):
@@ -752,9 +882,11 @@ class SpecDecodeWorker:
         """:666-720.  Prompts: W4A16 prefill, first token sampled by the target.  Decode sequences with speculation off
         for this step: the scorer alone, one token each.  A batch may hold both (prompts first, as vLLM orders them).
         Output: `_serialize_sampler_output_no_logprobs` (:582-664)."""
-        sgml = req.seq_group_metadata_list
+        groups = req.seq_group_metadata_list
+        sgml, owner = self._sequence_rows(groups)    # one row per sequence
         assert req.w4a4 is False
         tokens = [VLLM_INVALID_TOKEN_ID] * len(sgml)
+        more: Dict[int, list] = {}             # batch index of a prompt -> [token, logprob entry or None] per additional sample
         real: Dict[int, tuple] = {}            # batch index -> (rank, logprob, top ids, top logprobs) of its token
         prompt_real: Dict[int, list] = {}      # batch index -> its prompt_logprobs list
         prompts = [i for i, s in enumerate(sgml) if s.is_prompt]
@@ -766,9 +898,20 @@ class SpecDecodeWorker:
             self._check_out_of_cycle_errors("the prompt pass")
             for i, slot in zip(prompts, slots):
                 tokens[i] = int(first[slot])
+                group = self._group(sgml[i].request_id)
+                if group is not None:       # the samples' first tokens: what binds their sequence ids on the next step
+                    group.first = [int(first[b]) for b in group.slots]
+                    more[i] = [[t, None] for t in group.first[1:]]
             self.scorer_calls += 1          # one scorer call for the prompt batch, as in the reference
             if self._real_logprobs:
                 real.update(self._token_logprobs("first", [sgml[i] for i in prompts], prompts, slots, tokens))
+                for i in more:              # (per sample, as for a single sequence)
+                    sample_slots = self._group(sgml[i].request_id).slots[1:]
+                    n_top = self._num_logprobs(sgml[i])
+                    lp, rank, top, tlp = (t.tolist() for t in self.engine.token_logprobs(
+                        "first", sample_slots, [t for t, _ in more[i]], n_top))
+                    for j, entry in enumerate(more[i]):
+                        entry[1] = (rank[j], lp[j], top[j][:n_top], tlp[j][:n_top])
                 for i, slot in zip(prompts, slots):
                     got = self.engine.take_prompt_logprobs(slot)
                     if got is not None:
@@ -779,7 +922,22 @@ class SpecDecodeWorker:
                 tokens[i] = tok[slot]
             if self._real_logprobs:
                 real.update(self._token_logprobs("no_spec", [sgml[i] for i in decodes], decodes, dslots, tokens))
-        return [self._serialize_sampler_output_no_logprobs(sgml, tokens, real, prompt_real)]
+        return self._regroup([self._serialize_sampler_output_no_logprobs(sgml, tokens, real, prompt_real, more)], owner, len(groups))
+
+    @staticmethod
+    def _regroup(outs: List[SamplerOutput], owner: Optional[List[int]], num_groups: int) -> List[SamplerOutput]:
+        """Per-sequence rows back to `outputs[i]` = the i-th sequence group: the samples of a group's rows in one output."""
+        if owner is None:
+            return outs
+        for out in outs:
+            merged: List[Optional[CompletionSequenceGroupOutput]] = [None] * num_groups
+            for row, i in zip(out.outputs, owner):
+                if merged[i] is None:
+                    merged[i] = row
+                else:
+                    merged[i].samples.extend(row.samples)
+            out.outputs = merged
+        return outs
 
     def _token_logprobs(self, kind: str, sgs, idx: List[int], slots: List[int], tokens: List[int]) -> Dict[int, tuple]:
         """disable_logprobs=False on the paths outside the cycle (`_run_no_spec` returns the scorer's own SamplerOutput there,
@@ -815,10 +973,13 @@ class SpecDecodeWorker:
         return {b: int(out[b]) for b in dslots}
 
     def _serialize_sampler_output_no_logprobs(self, sgml, tokens: List[int], real: Optional[Dict[int, tuple]] = None,
-                                              prompt_real: Optional[Dict[int, list]] = None) -> SamplerOutput:
+                                              prompt_real: Optional[Dict[int, list]] = None,
+                                              more: Optional[Dict[int, list]] = None) -> SamplerOutput:
         """:582-664: only the token ids are populated; a sequence group without a sample (`do_sample` False: a
         non-terminal prompt chunk) still gets its own, empty, output.  real / prompt_real (disable_logprobs=False): the
-        entries that replace the dummies, by batch index."""
+        entries that replace the dummies, by batch index.  more: the additional samples of a prompt that starts several sequences,
+        [token, logprob entry or None] each -- all of a group's samples name the prompt's sequence as their parent, as the
+        reference's sampler does."""
         outs = []
         for i, (s, tok) in enumerate(zip(sgml, tokens)):
             if not s.do_sample:
@@ -834,6 +995,10 @@ class SpecDecodeWorker:
             rank, lp, top, tlp = real[i] if real and i in real else (-1, 0.0, [], [])
             outs.append(create_sequence_group_output(tok, rank, lp, seq_id, [v if v >= 0 else None for v in top], tlp,
                                                      prompt_logprobs))
+            for t, entry in (more or {}).get(i, ()):
+                rank, lp, top, tlp = entry if entry is not None else (-1, 0.0, [], [])
+                outs[-1].samples.append(SequenceOutput(parent_seq_id=seq_id, output_token=t, logprobs=create_logprobs_output(
+                    t, rank, lp, [v if v >= 0 else None for v in top], tlp)))
         return SamplerOutput(outputs=outs)
 
     def _run_speculative_decoding_step(self, req: ExecuteModelRequest, num_lookahead_slots: int) -> List[SamplerOutput]:
@@ -844,16 +1009,17 @@ class SpecDecodeWorker:
         if num_lookahead_slots != k:
             raise ValueError(f"num_lookahead_slots = {num_lookahead_slots}, but the cycle was captured for "
                              f"num_speculative_tokens = {k} (SpeculativeConfig.num_speculative_tokens)")
-        sgml = req.seq_group_metadata_list
-        if any(s.is_prompt for s in sgml):
+        groups = req.seq_group_metadata_list
+        if any(s.is_prompt for s in groups):
             raise NotImplementedError("prompt chunks inside a speculative step (chunked prefill) are not scheduled onto "
                                       "this worker: vLLM sends prompt-only batches with num_lookahead_slots == 0")
+        sgml, owner = self._sequence_rows(groups)    # one row per sequence
         slots = self._decode_slots(sgml)
         spec = [i for i, s in enumerate(sgml) if s.num_speculative_tokens != 0]
         nospec = [i for i, s in enumerate(sgml) if s.num_speculative_tokens == 0]
         req.w4a4 = True                                   # :799
         self.proposer_calls += k
-        scorer_req = req.clone(sgml)                      # mqa_scorer.py:65: clone drops w4a4 -> W4A16
+        scorer_req = req.clone(groups)                    # mqa_scorer.py:65: clone drops w4a4 -> W4A16
         assert scorer_req.w4a4 is False
         req.w4a4 = False                                  # :812
         self.scorer_calls += 1
@@ -876,7 +1042,7 @@ class SpecDecodeWorker:
             if self._real_logprobs:
                 riders = self._token_logprobs("no_spec", [sgml[i] for i in nospec], nospec, [slots[i] for i in nospec],
                                               [r[0] for r in rows])
-        return self._create_output_sampler_list(sgml, rows, k, slots, spec, cycle_real, riders)
+        return self._regroup(self._create_output_sampler_list(sgml, rows, k, slots, spec, cycle_real, riders), owner, len(groups))
 
     def _create_output_sampler_list(self, sgml, rows: List[List[int]], k: int, slots: List[int],
                                     spec: Optional[List[int]] = None, cycle_real=None,

@@ -67,7 +67,18 @@ _LOGPROBS_SCHEMA = ("(Tensor x, Tensor token_ids, int num_top, Tensor(a!) token_
 _op("token_logprobs_from_probs" + _LOGPROBS_SCHEMA, _none(ops.token_logprobs_from_probs))
 _op("token_logprobs_from_logits" + _LOGPROBS_SCHEMA, _none(ops.token_logprobs_from_logits))
 
+# KV block operations (torch.ops._C_cache_ops.copy_blocks / swap_blocks); block_mapping / block_ids: int64 [n, 2] / [n] on the host
+_op("copy_blocks(Tensor(a!)[] key_caches, Tensor(b!)[] value_caches, Tensor block_mapping) -> ()",
+    lambda key_caches, value_caches, block_mapping: ops.copy_blocks(ops.KVBlocks(key_caches, value_caches),
+                                                                    block_mapping.tolist()))
+_op("gather_blocks(Tensor[] key_caches, Tensor[] value_caches, Tensor block_ids, Tensor(a!) staging) -> ()",
+    lambda key_caches, value_caches, block_ids, staging: ops.gather_blocks(ops.KVBlocks(key_caches, value_caches),
+                                                                          block_ids.tolist(), staging))
+_op("scatter_blocks(Tensor(a!)[] key_caches, Tensor(b!)[] value_caches, Tensor block_ids, Tensor staging) -> ()",
+    lambda key_caches, value_caches, block_ids, staging: ops.scatter_blocks(ops.KVBlocks(key_caches, value_caches),
+                                                                           block_ids.tolist(), staging))
+
 OPS = ("rms_norm_general_fuse_sum_i4", "rms_norm_general_fuse_sum_fp16", "fuse_sym_quant", "faster_fast_hadamard_transform",
        "fast_hadamard_transform", "rowwise_scaled_linear_cutlass_s4s4_unified", "w4a16_matmul", "rotary_embedding",
        "reshape_and_cache_flash", "advance_step_flashattn", "process_logits", "logit_table_set_prompt", "logit_table_catch_up",
-       "process_logits_constrained", "token_logprobs_from_probs", "token_logprobs_from_logits")
+       "process_logits_constrained", "token_logprobs_from_probs", "token_logprobs_from_logits", "copy_blocks", "gather_blocks", "scatter_blocks")
