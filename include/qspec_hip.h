@@ -615,7 +615,13 @@ int qspec_spec_prepare_verify_embed(int batch, int k, int block_size, int max_bl
 
 /* SpecDecodeWorker._create_output_sampler_list bookkeeping (vllm/spec_decode/spec_decode_worker.py:972-1063):
  * append the emitted prefix of out_tokens[b] (-1 = nothing) to gen_tokens[b] (may be NULL), advance seq_lens,
- * last_token = last emitted token. */
+ * last_token = last emitted token.  The emitted prefix is everything before the first -1 (n tokens, 0 <= n <= k + 1; values
+ * behind that -1 are ignored; n == 0 changes nothing).  Capacity: token i of the prefix is stored at
+ * gen_tokens[b][gen_lens[b] + i] only while that index is below gen_capacity -- nothing is ever stored at or beyond it --
+ * but seq_lens, gen_lens (may be NULL when gen_tokens is) and last_token advance over all n tokens: gen_lens counts the
+ * emitted tokens, not the stored ones, so gen_lens[b] > gen_capacity tells the host that row b lost its tail.  The engine
+ * never gets there: gen_tokens is max_new_tokens + k + 1 wide and a cycle is refused on the host once gen_lens + k + 1
+ * would exceed that width. */
 int qspec_spec_commit(int batch, int k, const int64_t* out_tokens, int32_t* seq_lens, int64_t* last_token,
                       int64_t* gen_tokens, int32_t* gen_lens, int gen_capacity, void* stream);
 

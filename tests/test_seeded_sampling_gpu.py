@@ -8,32 +8,11 @@ import numpy as np
 import pytest
 import torch
 
+from philox_ref import philox_r0, seeded_r0  # noqa: F401  (numpy Philox4x32-10, shared with the engine-stream tests)
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 M32 = 0xFFFFFFFF
-
-
-# ------------------------------------------------------------------ numpy Philox4x32-10 (the kernel's, csrc/sampler.hip)
-
-def philox_r0(c0, c1, c2, c3, k0, k1):
-    """First output word of Philox4x32-10 for broadcastable uint32-valued arrays."""
-    u = np.uint64
-    c0, c1, c2, c3, k0, k1 = (np.asarray(x, dtype=u) for x in (c0, c1, c2, c3, k0, k1))
-    c0, c1, c2, c3, k0, k1 = np.broadcast_arrays(c0, c1, c2, c3, k0, k1)
-    m = u(M32)
-    for _ in range(10):
-        p0 = u(0xD2511F53) * c0
-        p1 = u(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> u(32)) ^ c1 ^ k0, p1 & m, (p0 >> u(32)) ^ c3 ^ k1, p0 & m
-        k0 = (k0 + u(0x9E3779B9)) & m
-        k1 = (k1 + u(0xBB67AE85)) & m
-    return c0
-
-
-def seeded_r0(c0, seed, base_pos, stream, j):
-    seed = np.asarray(seed, dtype=np.uint64)
-    c1 = np.uint64(0x80000000) | (np.uint64(stream) << np.uint64(16)) | np.asarray(j, dtype=np.uint64)
-    return philox_r0(c0, c1, np.asarray(base_pos, dtype=np.uint64), 0, seed & np.uint64(M32), seed >> np.uint64(32))
 
 
 def dev(a):
