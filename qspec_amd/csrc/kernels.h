@@ -180,53 +180,85 @@ int softmax_argmax(const f16* logits, float* probs, int64_t* token, int T, int V
 size_t head_softmax_ws_bytes(int rows);
 void* head_softmax_part_max(void* ws, int rows);
 int head_softmax_argmax(const f16* logits, float* probs, int64_t* token, int T, int V, int nparts, void* ws, hipStream_t st);
-int rejection_sample(const float* target_probs, const float* draft_probs, const int64_t* draft_ids,
-                     const int64_t* bonus_ids, const float* uniform, const float* exponential, uint64_t seed,
-                     uint64_t offset, uint64_t* rng_state, int B, int k, int V, int64_t dp_sb, int64_t dp_sk,
-                     int64_t di_sb, int64_t di_sk, int64_t bonus_stride, int64_t* out_tokens, uint8_t* accepted,
-                     int64_t* recovered, int64_t* counters, const int32_t* active_lens, void* ws, hipStream_t st);
-int rejection_sample_seeded(const float* target_probs, const float* draft_probs, const int64_t* draft_ids,
-                            const int64_t* bonus_ids, const float* uniform, const float* exponential, uint64_t seed,
-                            uint64_t offset, uint64_t* rng_state, int B, int k, int V, int64_t dp_sb, int64_t dp_sk,
-                            int64_t di_sb, int64_t di_sk, int64_t bonus_stride, int64_t* out_tokens, uint8_t* accepted,
-                            int64_t* recovered, int64_t* counters, const int32_t* active_lens, const int64_t* seq_seeds,
-                            const int32_t* seq_seeded, const int32_t* base_pos, void* ws, hipStream_t st);
+// Per-sequence seeded draws (sampler.hip, "Per-sequence seeded draws"); seeds == NULL: every row draws from the engine stream
+struct SeedRows {
+    const int64_t* seeds;      // [nseq]
+    const int32_t* seeded;     // [nseq], 0 = the engine stream
+    const int32_t* base_pos;   // [nseq]
+    int rows_per_seq;          // row t -> sequence t / rows_per_seq, j = j_base + t % rows_per_seq
+    int j_base;
+    uint32_t stream;           // 1 draft sample, 2 target sample, 3 rejection exponential, 4 rejection uniform
+};
+struct RejectionArgs {
+    const float *target_probs, *draft_probs;
+    const int64_t *draft_ids, *bonus_ids;
+    const float *uniform, *exponential;
+    uint64_t seed, offset;
+    uint64_t* rng_state;
+    int B, k, V;
+    int64_t dp_sb, dp_sk, di_sb, di_sk, bonus_stride;
+    int64_t* out_tokens;
+    uint8_t* accepted;
+    int64_t *recovered, *counters;
+    const int32_t* active_lens;
+    SeedRows sr;   // sequence b = batch row b: the three arrays are [B]; the kernels map (b, i) and the stream themselves
+    void* ws;
+};
+int rejection_sample(const RejectionArgs& a, hipStream_t st);
 size_t sample_ws_bytes(int rows);
-int sample_top_k_top_p(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
-                       const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
-                       int64_t* token, int64_t token_stride, int T, int V, void* ws, hipStream_t st);
-int sample_top_k_top_p_seeded(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
-                              const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
-                              int64_t* token, int64_t token_stride, int T, int V, const int64_t* seq_seeds,
-                              const int32_t* seq_seeded, const int32_t* base_pos, int nseq, int rows_per_seq, int j_base,
-                              int draw_stream, void* ws, hipStream_t st);
-int sample_top_k_top_p_min_p(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
-                             const float* min_p, const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state,
-                             float* probs, int64_t* token, int64_t token_stride, int T, int V, void* ws, hipStream_t st);
-int sample_top_k_top_p_min_p_seeded(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
-                                    const float* min_p, const float* exponential, uint64_t seed, uint64_t offset,
-                                    uint64_t* rng_state, float* probs, int64_t* token, int64_t token_stride, int T, int V,
-                                    const int64_t* seq_seeds, const int32_t* seq_seeded, const int32_t* base_pos, int nseq,
-                                    int rows_per_seq, int j_base, int draw_stream, void* ws, hipStream_t st);
+struct SampleArgs {
+    const f16* logits;
+    const float* temperature;
+    const int32_t* top_k;
+    const float *top_p, *min_p;   // min_p [T] fp32 per row, or NULL: none -- the selection kernel without it, bit for bit
+    const float* exponential;
+    uint64_t seed, offset;
+    uint64_t* rng_state;
+    float* probs;
+    int64_t* token;
+    int64_t token_stride;
+    int T, V;
+    SeedRows sr;
+    int nseq;                     // rows of sr's arrays
+    void* ws;
+};
+int sample_top_k_top_p(const SampleArgs& a, hipStream_t st);
 // logit processors (min_tokens, repetition / frequency / presence penalties) and the per-slot token table they read
 int logit_table_set_prompt(uint32_t* table, int V, int slot, const int64_t* prompt, int n_prompt, const int64_t* outputs,
                            int n_out, int32_t* counted_len, hipStream_t st);
 int logit_table_catch_up(int B, int V, uint32_t* table, int32_t* counted_len, const int32_t* need, const int64_t* gen_tokens,
                          int gen_cap, const int32_t* gen_lens, hipStream_t st);
-int process_logits(const f16* logits, f16* out, int T, int V, const uint32_t* table, const int32_t* slot_ids,
-                   const int32_t* active_lens, const f16* rep, const f16* freq, const f16* pres, const int32_t* min_tokens,
-                   const int32_t* gen_base, const int32_t* gen_lens, const int32_t* stop_ids, const int32_t* n_stop,
-                   const int64_t* draft_ids, int64_t di_sb, int64_t di_sk, int rows_per_seq, int j_base, int nslots,
-                   int stop_width, hipStream_t st);
-// token constraints (logit_bias, allowed_token_ids, bad words) in front of the pipeline above, inside the same launch
-int process_logits_constrained(const f16* logits, f16* out, int T, int V, const uint32_t* table, const int32_t* slot_ids,
-                               const int32_t* active_lens, const f16* rep, const f16* freq, const f16* pres,
-                               const int32_t* min_tokens, const int32_t* gen_base, const int32_t* gen_lens,
-                               const int32_t* stop_ids, const int32_t* n_stop, const int64_t* draft_ids, int64_t di_sb,
-                               int64_t di_sk, int rows_per_seq, int j_base, int nslots, int stop_width, const uint32_t* deny,
-                               int deny_words, const int32_t* meta, const int32_t* bias_ids, const float* bias_vals,
-                               const int32_t* words, const int32_t* word_lens, const int32_t* tail, const int64_t* gen_tokens,
-                               int gen_cap, hipStream_t st);
+struct LpArgs {
+    const f16* logits;            // [T, V] raw
+    f16* out;                     // [T, V] processed (out of place)
+    const uint32_t* table;        // [nslots, V]
+    const int32_t* slot_ids;      // [nseq] slot of sequence s, or NULL: s itself
+    const int32_t* active_lens;   // [nslots] or NULL: a slot with active_lens <= 0 is copied through
+    const f16 *rep, *freq, *pres; // [nslots]
+    const int32_t* min_tokens;    // [nslots]
+    const int32_t* gen_base;      // [nslots] outputs the request had before admission
+    const int32_t* gen_lens;      // [nslots] outputs committed since (at the start of the cycle)
+    const int32_t* stop_ids;      // [nslots, stop_width]
+    const int32_t* n_stop;        // [nslots]
+    const int64_t* draft_ids;     // in-flight token i (0-based) of slot b at b * di_sb + i * di_sk; NULL: none
+    int64_t di_sb, di_sk;
+    int V, rows_per_seq, j_base, nslots, stop_width;   // stop_width <= QS_LP_MAX_STOP: row width of stop_ids
+};
+// token constraints (logit_bias, allowed_token_ids, bad words) in front of the pipeline above, inside the same launch: the
+// per-slot state sampler.hip describes ("Token constraints"); deny == NULL: none
+struct LpCons {
+    const uint32_t* deny;
+    const int32_t* meta;
+    const int32_t* bias_ids;
+    const float* bias_vals;
+    const int32_t* words;
+    const int32_t* word_lens;
+    const int32_t* tail;
+    const int64_t* gen_tokens;    // [nslots, gen_cap] the outputs committed since admission
+    int gen_cap, deny_words;
+};
+struct LpArgsC : LpArgs { LpCons c; };
+int process_logits(const LpArgsC& a, int T, hipStream_t st);
 int token_constraints_set(uint32_t* deny, int deny_words, int32_t* meta, int32_t* bias_ids, float* bias_vals, int32_t* words,
                           int32_t* word_lens, int V, int slot, const int64_t* allowed, int n_allowed, const int64_t* banned,
                           int n_banned, const int32_t* src_bias_ids, const float* src_bias_vals, int n_bias,

@@ -203,16 +203,9 @@ __device__ __forceinline__ float u01_open(uint32_t x) { return ((float)(x >> 8) 
 //   key = (seed lo, seed hi), counter = (c0, 0x80000000 | stream << 16 | j, base_pos, 0)
 // c0 = v (per-token noise) or 0xFFFFFFFF (accept uniform).  Rows of unseeded sequences keep the engine stream's
 // (seed, offset) key and counter bit for bit.  Every pointer is read at replay (captured graphs serve changing seeds).
+// SeedRows (kernels.h) carries the per-sequence arrays.
 struct PhiloxKey {
     uint32_t k0, k1, c1, c2, c3;
-};
-struct SeedRows {
-    const int64_t* seeds;      // [nseq]
-    const int32_t* seeded;     // [nseq], 0 = the engine stream
-    const int32_t* base_pos;   // [nseq]
-    int rows_per_seq;          // row t -> sequence t / rows_per_seq, j = j_base + t % rows_per_seq
-    int j_base;
-    uint32_t stream;           // 1 draft sample, 2 target sample, 3 rejection exponential, 4 rejection uniform
 };
 __device__ __forceinline__ PhiloxKey engine_key(uint64_t seed, uint64_t offset, uint32_t c1) {
     return PhiloxKey{(uint32_t)seed, (uint32_t)(seed >> 32), c1, (uint32_t)offset, (uint32_t)(offset >> 32)};
@@ -378,47 +371,26 @@ __global__ __launch_bounds__(1024) void rejection_output_kernel(
     if (rng_state && threadIdx.x == 0) rng_state[1] = offset + 1;  // after every draw of this call
 }
 
-template <bool SEEDED>
-static int rejection_sample_impl(const float* target_probs, const float* draft_probs, const int64_t* draft_ids,
-                                 const int64_t* bonus_ids, const float* uniform, const float* exponential, uint64_t seed,
-                                 uint64_t offset, uint64_t* rng_state, int B, int k, int V, int64_t dp_sb, int64_t dp_sk,
-                                 int64_t di_sb, int64_t di_sk, int64_t bonus_stride, int64_t* out_tokens, uint8_t* accepted,
-                                 int64_t* recovered, int64_t* counters, const int32_t* active_lens, SeedRows sr, void* ws,
-                                 hipStream_t st) {
-    if (B == 0) return 0;
-    if (k < 1) return -1;
-    SmPartA* part_a = reinterpret_cast<SmPartA*>(ws);
-    double* part_s = reinterpret_cast<double*>(reinterpret_cast<char*>(ws) + (size_t)B * k * QS_SM_CHUNKS * 8);
-    hipLaunchKernelGGL(rejection_sum_kernel, dim3(QS_SM_CHUNKS, B * k), dim3(256), 0, st, target_probs, draft_probs, k,
-                       V, dp_sb, dp_sk, part_s);
-    hipLaunchKernelGGL(rejection_argmax_kernel<SEEDED>, dim3(QS_SM_CHUNKS, B * k), dim3(256), 0, st, target_probs, draft_probs,
-                       exponential, seed, offset, rng_state, k, V, dp_sb, dp_sk, part_s, part_a, sr);
-    hipLaunchKernelGGL(rejection_output_kernel<SEEDED>, dim3(1), dim3(1024), 0, st, target_probs, draft_probs, draft_ids,
-                       bonus_ids, uniform, seed, offset, rng_state, part_a, B, k, V, dp_sb, dp_sk, di_sb, di_sk,
-                       bonus_stride, accepted, recovered, out_tokens, counters, active_lens, sr);
+int rejection_sample(const RejectionArgs& a, hipStream_t st) {
+    auto argmax_kernel = rejection_argmax_kernel<false>;
+    auto output_kernel = rejection_output_kernel<false>;
+    if (a.sr.seeds) {   // the SEEDED instantiations follow the presence of the seed arrays
+        if (!a.sr.seeded || !a.sr.base_pos) return -1;
+        argmax_kernel = rejection_argmax_kernel<true>;
+        output_kernel = rejection_output_kernel<true>;
+    }
+    if (a.B == 0) return 0;
+    if (a.k < 1) return -1;
+    SmPartA* part_a = reinterpret_cast<SmPartA*>(a.ws);
+    double* part_s = reinterpret_cast<double*>(reinterpret_cast<char*>(a.ws) + (size_t)a.B * a.k * QS_SM_CHUNKS * 8);
+    hipLaunchKernelGGL(rejection_sum_kernel, dim3(QS_SM_CHUNKS, a.B * a.k), dim3(256), 0, st, a.target_probs, a.draft_probs, a.k,
+                       a.V, a.dp_sb, a.dp_sk, part_s);
+    hipLaunchKernelGGL(argmax_kernel, dim3(QS_SM_CHUNKS, a.B * a.k), dim3(256), 0, st, a.target_probs, a.draft_probs,
+                       a.exponential, a.seed, a.offset, a.rng_state, a.k, a.V, a.dp_sb, a.dp_sk, part_s, part_a, a.sr);
+    hipLaunchKernelGGL(output_kernel, dim3(1), dim3(1024), 0, st, a.target_probs, a.draft_probs, a.draft_ids, a.bonus_ids,
+                       a.uniform, a.seed, a.offset, a.rng_state, part_a, a.B, a.k, a.V, a.dp_sb, a.dp_sk, a.di_sb, a.di_sk,
+                       a.bonus_stride, a.accepted, a.recovered, a.out_tokens, a.counters, a.active_lens, a.sr);
     return 0;
-}
-int rejection_sample(const float* target_probs, const float* draft_probs, const int64_t* draft_ids,
-                     const int64_t* bonus_ids, const float* uniform, const float* exponential, uint64_t seed,
-                     uint64_t offset, uint64_t* rng_state, int B, int k, int V, int64_t dp_sb, int64_t dp_sk,
-                     int64_t di_sb, int64_t di_sk, int64_t bonus_stride, int64_t* out_tokens, uint8_t* accepted,
-                     int64_t* recovered, int64_t* counters, const int32_t* active_lens, void* ws, hipStream_t st) {
-    return rejection_sample_impl<false>(target_probs, draft_probs, draft_ids, bonus_ids, uniform, exponential, seed, offset,
-                                        rng_state, B, k, V, dp_sb, dp_sk, di_sb, di_sk, bonus_stride, out_tokens, accepted,
-                                        recovered, counters, active_lens, SeedRows{}, ws, st);
-}
-// sequence b = batch row b: seq_seeds / seq_seeded / base_pos are [B]
-int rejection_sample_seeded(const float* target_probs, const float* draft_probs, const int64_t* draft_ids,
-                            const int64_t* bonus_ids, const float* uniform, const float* exponential, uint64_t seed,
-                            uint64_t offset, uint64_t* rng_state, int B, int k, int V, int64_t dp_sb, int64_t dp_sk,
-                            int64_t di_sb, int64_t di_sk, int64_t bonus_stride, int64_t* out_tokens, uint8_t* accepted,
-                            int64_t* recovered, int64_t* counters, const int32_t* active_lens, const int64_t* seq_seeds,
-                            const int32_t* seq_seeded, const int32_t* base_pos, void* ws, hipStream_t st) {
-    if (!seq_seeds || !seq_seeded || !base_pos) return -1;
-    const SeedRows sr{seq_seeds, seq_seeded, base_pos, 1, 0, 0u};   // (the kernels map (b, i) and the stream themselves)
-    return rejection_sample_impl<true>(target_probs, draft_probs, draft_ids, bonus_ids, uniform, exponential, seed, offset,
-                                       rng_state, B, k, V, dp_sb, dp_sk, di_sb, di_sk, bonus_stride, out_tokens, accepted,
-                                       recovered, counters, active_lens, sr, ws, st);
 }
 
 // ---------------------------------------------------------------- typical acceptance (MEDUSA 3.3.1)
@@ -804,14 +776,22 @@ __global__ __launch_bounds__(256) void topk_token_kernel(const SmPartA* __restri
 size_t sample_ws_bytes(int rows) {
     return (size_t)rows * QS_TK_KEYS * 4 + (size_t)rows * sizeof(TkRow) + (size_t)rows * QS_SM_CHUNKS * sizeof(SmPartA);
 }
-static bool g_tk_hist_attr = false;   // topk_hist_kernel's LDS attribute is set (shared by both instantiations)
-template <bool SEEDED>
-static int sample_top_k_top_p_impl(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
-                                   const float* min_p, const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
-                                   int64_t* token, int64_t token_stride, int T, int V, SeedRows sr, void* ws, hipStream_t st) {
+static bool g_tk_hist_attr = false;   // topk_hist_kernel's LDS attribute is set
+int sample_top_k_top_p(const SampleArgs& a, hipStream_t st) {
+    // the instantiations follow the presence of the optional parts: MINP of a.min_p, SEEDED of the seed arrays
+    const auto select_kernel = a.min_p ? topk_select_kernel<true> : topk_select_kernel<false>;
+    auto write_kernel = topk_write_kernel<false>;
+    const SeedRows& sr = a.sr;
+    if (sr.seeds) {
+        if (!sr.seeded || !sr.base_pos || sr.rows_per_seq < 1 || (int64_t)a.nseq * sr.rows_per_seq < a.T || sr.j_base < 0 ||
+            sr.j_base + sr.rows_per_seq > 65536 || sr.stream < 1 || sr.stream > 0x7FFF)
+            return -1;
+        write_kernel = topk_write_kernel<true>;
+    }
+    const int T = a.T, V = a.V;
     if (T == 0) return 0;
-    uint32_t* hist = reinterpret_cast<uint32_t*>(ws);
-    TkRow* rows = reinterpret_cast<TkRow*>(reinterpret_cast<char*>(ws) + (size_t)T * QS_TK_KEYS * 4);
+    uint32_t* hist = reinterpret_cast<uint32_t*>(a.ws);
+    TkRow* rows = reinterpret_cast<TkRow*>(reinterpret_cast<char*>(a.ws) + (size_t)T * QS_TK_KEYS * 4);
     SmPartA* part_a = reinterpret_cast<SmPartA*>(reinterpret_cast<char*>(rows) + (size_t)T * sizeof(TkRow));
     if (!g_tk_hist_attr) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(topk_hist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -819,52 +799,12 @@ static int sample_top_k_top_p_impl(const f16* logits, const float* temperature, 
             return -8;
         g_tk_hist_attr = true;
     }
-    hipLaunchKernelGGL(topk_hist_kernel, dim3((V + QS_TK_HCHUNK - 1) / QS_TK_HCHUNK, T), dim3(1024), QS_TK_KEYS * 2, st, logits, hist, V);
-    if (min_p)
-        hipLaunchKernelGGL(topk_select_kernel<true>, dim3(T), dim3(1024), 0, st, hist, temperature, top_k, top_p, min_p, rows, V);
-    else
-        hipLaunchKernelGGL(topk_select_kernel<false>, dim3(T), dim3(1024), 0, st, hist, temperature, top_k, top_p, nullptr, rows, V);
-    hipLaunchKernelGGL(topk_write_kernel<SEEDED>, dim3(QS_SM_CHUNKS, T), dim3(256), 0, st, logits, rows, exponential, seed, offset,
-                       rng_state, probs, part_a, V, sr);
-    hipLaunchKernelGGL(topk_token_kernel, dim3(1), dim3(256), 0, st, part_a, token, token_stride, rng_state, T);
+    hipLaunchKernelGGL(topk_hist_kernel, dim3((V + QS_TK_HCHUNK - 1) / QS_TK_HCHUNK, T), dim3(1024), QS_TK_KEYS * 2, st, a.logits, hist, V);
+    hipLaunchKernelGGL(select_kernel, dim3(T), dim3(1024), 0, st, hist, a.temperature, a.top_k, a.top_p, a.min_p, rows, V);
+    hipLaunchKernelGGL(write_kernel, dim3(QS_SM_CHUNKS, T), dim3(256), 0, st, a.logits, rows, a.exponential, a.seed, a.offset,
+                       a.rng_state, a.probs, part_a, V, sr);
+    hipLaunchKernelGGL(topk_token_kernel, dim3(1), dim3(256), 0, st, part_a, a.token, a.token_stride, a.rng_state, T);
     return 0;
-}
-int sample_top_k_top_p(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
-                       const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
-                       int64_t* token, int64_t token_stride, int T, int V, void* ws, hipStream_t st) {
-    return sample_top_k_top_p_impl<false>(logits, temperature, top_k, top_p, nullptr, exponential, seed, offset, rng_state, probs,
-                                          token, token_stride, T, V, SeedRows{}, ws, st);
-}
-int sample_top_k_top_p_seeded(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
-                              const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state, float* probs,
-                              int64_t* token, int64_t token_stride, int T, int V, const int64_t* seq_seeds,
-                              const int32_t* seq_seeded, const int32_t* base_pos, int nseq, int rows_per_seq, int j_base,
-                              int draw_stream, void* ws, hipStream_t st) {
-    if (!seq_seeds || !seq_seeded || !base_pos || rows_per_seq < 1 || (int64_t)nseq * rows_per_seq < T || j_base < 0 ||
-        j_base + rows_per_seq > 65536 || draw_stream < 1 || draw_stream > 0x7FFF)
-        return -1;
-    const SeedRows sr{seq_seeds, seq_seeded, base_pos, rows_per_seq, j_base, (uint32_t)draw_stream};
-    return sample_top_k_top_p_impl<true>(logits, temperature, top_k, top_p, nullptr, exponential, seed, offset, rng_state, probs,
-                                         token, token_stride, T, V, sr, ws, st);
-}
-// min_p [T] fp32 per row (NULL: none -- the selection kernel of the entries above); everything else as there
-int sample_top_k_top_p_min_p(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
-                             const float* min_p, const float* exponential, uint64_t seed, uint64_t offset, uint64_t* rng_state,
-                             float* probs, int64_t* token, int64_t token_stride, int T, int V, void* ws, hipStream_t st) {
-    return sample_top_k_top_p_impl<false>(logits, temperature, top_k, top_p, min_p, exponential, seed, offset, rng_state, probs,
-                                          token, token_stride, T, V, SeedRows{}, ws, st);
-}
-int sample_top_k_top_p_min_p_seeded(const f16* logits, const float* temperature, const int32_t* top_k, const float* top_p,
-                                    const float* min_p, const float* exponential, uint64_t seed, uint64_t offset,
-                                    uint64_t* rng_state, float* probs, int64_t* token, int64_t token_stride, int T, int V,
-                                    const int64_t* seq_seeds, const int32_t* seq_seeded, const int32_t* base_pos, int nseq,
-                                    int rows_per_seq, int j_base, int draw_stream, void* ws, hipStream_t st) {
-    if (!seq_seeds || !seq_seeded || !base_pos || rows_per_seq < 1 || (int64_t)nseq * rows_per_seq < T || j_base < 0 ||
-        j_base + rows_per_seq > 65536 || draw_stream < 1 || draw_stream > 0x7FFF)
-        return -1;
-    const SeedRows sr{seq_seeds, seq_seeded, base_pos, rows_per_seq, j_base, (uint32_t)draw_stream};
-    return sample_top_k_top_p_impl<true>(logits, temperature, top_k, top_p, min_p, exponential, seed, offset, rng_state, probs,
-                                         token, token_stride, T, V, sr, ws, st);
 }
 
 // ---------------------------------------------------------------- logit processors
@@ -963,22 +903,7 @@ __device__ __forceinline__ f16 lp_element(f16 x, int v, uint32_t w, const LpRow&
     x = f2h(h2f(x) - h2f(f2h(h2f(r.pres) * (cnt > 0u ? 1.0f : 0.0f))));
     return x;
 }
-struct LpArgs {
-    const f16* logits;            // [T, V] raw
-    f16* out;                     // [T, V] processed (out of place)
-    const uint32_t* table;        // [nslots, V]
-    const int32_t* slot_ids;      // [nseq] slot of sequence s, or NULL: s itself
-    const int32_t* active_lens;   // [nslots] or NULL: a slot with active_lens <= 0 is copied through
-    const f16 *rep, *freq, *pres; // [nslots]
-    const int32_t* min_tokens;    // [nslots]
-    const int32_t* gen_base;      // [nslots] outputs the request had before admission
-    const int32_t* gen_lens;      // [nslots] outputs committed since (at the start of the cycle)
-    const int32_t* stop_ids;      // [nslots, stop_width]
-    const int32_t* n_stop;        // [nslots]
-    const int64_t* draft_ids;     // in-flight token i (0-based) of slot b at b * di_sb + i * di_sk; NULL: none
-    int64_t di_sb, di_sk;
-    int V, rows_per_seq, j_base, nslots, stop_width;   // stop_width <= QS_LP_MAX_STOP: row width of stop_ids
-};
+// LpArgs (kernels.h): the launch arguments of the pass
 // Token constraints (logit_bias, allowed_token_ids, bad words): the reference's engine lowers them to logits processors
 // (vllm/engine/llm_engine.py:1950-2009; vllm/entrypoints/openai/logits_processors.py:10-50; vllm/logits_process.py:48-119) that
 // run on the fp16 row in front of Sampler.forward (vllm/model_executor/layers/logits_processor.py:134-170).  Per-slot state:
@@ -990,18 +915,7 @@ struct LpArgs {
 #define QS_TC_MAX_BIAS 512     // QS_MAX_LOGIT_BIAS of include/qspec_hip.h
 #define QS_TC_MAX_WORDS 32     // QS_MAX_BAD_WORDS
 #define QS_TC_WORD_LEN 8       // QS_MAX_BAD_WORD_LEN
-struct LpCons {
-    const uint32_t* deny;
-    const int32_t* meta;
-    const int32_t* bias_ids;
-    const float* bias_vals;
-    const int32_t* words;
-    const int32_t* word_lens;
-    const int32_t* tail;
-    const int64_t* gen_tokens;    // [nslots, gen_cap] the outputs committed since admission
-    int gen_cap, deny_words;
-};
-struct LpArgsC : LpArgs { LpCons c; };
+// LpCons, LpArgsC (kernels.h): that per-slot state, behind the arguments of the plain pass
 template <bool C> struct LpArgsOf { typedef LpArgs type; };
 template <> struct LpArgsOf<true> { typedef LpArgsC type; };
 // grid (chunks of 2048 logits, rows): 16-byte loads of the logits and of the table words, 16-byte stores; a row is wave-uniform
@@ -1166,37 +1080,19 @@ __global__ __launch_bounds__(256) void process_logits_kernel(typename LpArgsOf<C
         }
     }
 }
-static bool lp_args_ok(int V, int rows_per_seq, int j_base, int nslots, int stop_width) {
-    return !(stop_width < 0 || stop_width > QS_LP_MAX_STOP || nslots < 1 || rows_per_seq < 1 || j_base < 0 ||
-             j_base + rows_per_seq - 1 > QS_LP_MAX_INFLIGHT);
-}
-int process_logits(const f16* logits, f16* out, int T, int V, const uint32_t* table, const int32_t* slot_ids,
-                   const int32_t* active_lens, const f16* rep, const f16* freq, const f16* pres, const int32_t* min_tokens,
-                   const int32_t* gen_base, const int32_t* gen_lens, const int32_t* stop_ids, const int32_t* n_stop,
-                   const int64_t* draft_ids, int64_t di_sb, int64_t di_sk, int rows_per_seq, int j_base, int nslots,
-                   int stop_width, hipStream_t st) {
+// the kernel instantiation (<C>) follows the presence of a.c.deny
+int process_logits(const LpArgsC& a, int T, hipStream_t st) {
     if (T == 0) return 0;
-    if (!lp_args_ok(V, rows_per_seq, j_base, nslots, stop_width)) return -1;
-    LpArgs a{logits, out, table, slot_ids, active_lens, rep, freq, pres, min_tokens, gen_base, gen_lens, stop_ids, n_stop,
-             draft_ids, di_sb, di_sk, V, rows_per_seq, j_base, nslots, stop_width};
-    hipLaunchKernelGGL(process_logits_kernel<false>, dim3((V + QS_LP_CHUNK - 1) / QS_LP_CHUNK, T), dim3(256), 0, st, a);
-    return 0;
-}
-int process_logits_constrained(const f16* logits, f16* out, int T, int V, const uint32_t* table, const int32_t* slot_ids,
-                               const int32_t* active_lens, const f16* rep, const f16* freq, const f16* pres,
-                               const int32_t* min_tokens, const int32_t* gen_base, const int32_t* gen_lens,
-                               const int32_t* stop_ids, const int32_t* n_stop, const int64_t* draft_ids, int64_t di_sb,
-                               int64_t di_sk, int rows_per_seq, int j_base, int nslots, int stop_width, const uint32_t* deny,
-                               int deny_words, const int32_t* meta, const int32_t* bias_ids, const float* bias_vals,
-                               const int32_t* words, const int32_t* word_lens, const int32_t* tail, const int64_t* gen_tokens,
-                               int gen_cap, hipStream_t st) {
-    if (T == 0) return 0;
-    if (!lp_args_ok(V, rows_per_seq, j_base, nslots, stop_width) || gen_cap < 1 || (int64_t)deny_words * 32 < V) return -1;
-    LpArgsC a;
-    static_cast<LpArgs&>(a) = LpArgs{logits, out, table, slot_ids, active_lens, rep, freq, pres, min_tokens, gen_base, gen_lens,
-                                     stop_ids, n_stop, draft_ids, di_sb, di_sk, V, rows_per_seq, j_base, nslots, stop_width};
-    a.c = LpCons{deny, meta, bias_ids, bias_vals, words, word_lens, tail, gen_tokens, gen_cap, deny_words};
-    hipLaunchKernelGGL(process_logits_kernel<true>, dim3((V + QS_LP_CHUNK - 1) / QS_LP_CHUNK, T), dim3(256), 0, st, a);
+    if (a.stop_width < 0 || a.stop_width > QS_LP_MAX_STOP || a.nslots < 1 || a.rows_per_seq < 1 || a.j_base < 0 ||
+        a.j_base + a.rows_per_seq - 1 > QS_LP_MAX_INFLIGHT)
+        return -1;
+    const dim3 grid((a.V + QS_LP_CHUNK - 1) / QS_LP_CHUNK, T);
+    if (!a.c.deny) {
+        hipLaunchKernelGGL(process_logits_kernel<false>, grid, dim3(256), 0, st, static_cast<const LpArgs&>(a));
+        return 0;
+    }
+    if (a.c.gen_cap < 1 || (int64_t)a.c.deny_words * 32 < a.V) return -1;
+    hipLaunchKernelGGL(process_logits_kernel<true>, grid, dim3(256), 0, st, a);
     return 0;
 }
 // Admission (outside the graph): ONE workgroup builds the slot's deny row -- all ones where the request has allowed_token_ids,
