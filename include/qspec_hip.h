@@ -402,7 +402,7 @@ int qspec_rejection_sample(const float* target_with_bonus_probs, const int64_t* 
  *   exponential [tokens, vocab] fp32: injected draws (tests); NULL -> Philox(seed, offset) as qspec_rejection_sample, with
  *   rng_state (device uint64[2]) overriding the scalars and advanced by the call.
  *   Tokens with EQUAL logits at the top-p boundary are kept or masked together (the reference's unstable sort splits such a
- *   group arbitrarily); everything else follows the reference element for element.
+ *   group arbitrarily; +0.0 and -0.0 are equal logits); everything else follows the reference element for element.
  *   workspace: qspec_sample_workspace_bytes(tokens), zero-filled ONCE by the caller (every call leaves it zeroed). */
 size_t qspec_sample_workspace_bytes(int rows);
 int qspec_sample_top_k_top_p(const qspec_half* logits, const float* temperature, const int32_t* top_k, const float* top_p,

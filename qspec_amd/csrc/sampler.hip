@@ -483,7 +483,10 @@ int typical_acceptance_sample(const float* target_probs, const int64_t* draft_id
 // combines them.  The histogram is left zeroed for the next call.
 #define QS_TK_KEYS 65536
 __device__ __forceinline__ uint32_t tk_key(f16 h) {   // order-preserving: larger logit -> larger key
-    const uint16_t b = __builtin_bit_cast(uint16_t, h);
+    // -0.0 takes the key of +0.0: the two are EQUAL logits (a negative penalty produces -0.0), and a group of equal logits
+    // is one key, kept or masked as a whole
+    const uint16_t raw = __builtin_bit_cast(uint16_t, h);
+    const uint16_t b = raw == 0x8000u ? (uint16_t)0u : raw;
     return (b & 0x8000u) ? (uint32_t)(uint16_t)~b : (uint32_t)(b | 0x8000u);
 }
 __device__ __forceinline__ float tk_val(uint32_t key) {   // the logit of a key
@@ -654,7 +657,10 @@ __global__ __launch_bounds__(1024) void topk_select_kernel(uint32_t* __restrict_
     // everything below it; a group of equal logits is kept or masked as a whole.  The mass above a key never decreases along
     // the positions, so the answer lies in the thread where it crosses p Z_k -- or, if it crosses behind that thread's last
     // key, it is the first key of a later thread: those offer theirs without a walk, the smallest position wins.
-    {
+    // top_p >= 1 (the default) masks nothing and is not searched: with thr = Z_k the groups whose weight is below half an ulp
+    // of the fp64 mass above them (~37 nats under the maximum) would satisfy mass_above >= thr and be masked, tokens whose
+    // fp32 probability is not 0 -- the reference's `cumsum <= 1 - p` masks none of them
+    if (pp < 1.0) {
         const double thr = pp * zk;
         uint32_t best = 0xFFFFFFFFu;
         if (c_loc && m_ex + m_loc >= thr && 64u * tid <= pos_k) {

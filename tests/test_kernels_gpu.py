@@ -1635,9 +1635,9 @@ def test_sample_top_k_top_p_reference_fixture(ops, oracle, golden_dir):
 
 
 def test_sample_top_k_top_p_edge_rows_and_full_vocabulary(ops, oracle):
-    """Edge rows against the oracle (whose rule is the reference's, test_oracle_golden.py): a uniform row (every logit equal:
-    one group of V tokens -- kept whole whatever top-k / top-p say, a 128 k count in one histogram bin), a row at the fp16
-    ceiling, -inf logits (never kept), top_k = 1, top_p -> 0, a vocabulary that is no multiple of 8; then the full Llama-3
+    """Edge rows against the oracle (whose rule is the reference's, test_oracle_golden.py): a uniform row of 1003 tokens (every
+    logit equal: one group of V tokens -- kept whole whatever top-k / top-p say; the 131080-token one, a 128 k count in one
+    histogram bin, is a row of the selection matrix, test_sampling_cases_gpu.py), a row at the fp16 ceiling, -inf logits (never kept), top_k = 1, top_p -> 0, a vocabulary that is no multiple of 8; then the full Llama-3
     vocabulary at 16 rows (the verify pass's shape) with DISTINCT-per-row-ordering logits: kept sets equal, tokens equal."""
     rng = np.random.default_rng(5)
     V = 1003
