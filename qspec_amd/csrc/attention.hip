@@ -788,7 +788,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void paged_attention_wave
         QS_AWST();  // loop top: the slice's K and V have arrived (stamp build only: waits for everything)
         const int nkeys = max(0, min(k_end - sb, QS_AW_KEYS));
         // ---- S = Q K^T: lane holds rows 4 g4 + reg, key column t2 * 16 + c16.  Each K register is refilled with the
-        // wave's NEXT slice right behind its last use (as the weight ring of gemm_stream.hip): the loads never stop.
+        // wave's NEXT slice right behind its last use (as the weight ring of gemm_stream_w4a4.hip): the loads never stop.
         f32x4 sacc[2];
 #pragma unroll
         for (int t2 = 0; t2 < 2; t2++) {

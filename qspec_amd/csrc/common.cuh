@@ -8,7 +8,7 @@
 namespace qspec {
 
 // FRAGMENT-MAJOR layout of a 16-row fp16 activation tile [16, K] (K % 128 == 0), the layout the W4A16 streaming kernel's
-// MFMA fragments have (gemm_stream.hip, XP): [K / 128 steps][4 dwords][4 k-groups][16 rows][8 halves in the dequantiser's
+// MFMA fragments have (gemm_stream_w4a16.hip, XP): [K / 128 steps][4 dwords][4 k-groups][16 rows][8 halves in the dequantiser's
 // order 0,4,1,5,2,6,3,7].  A wave then takes a fragment with ONE fully coalesced 1-KiB load instead of the workgroup copying
 // the tile through LDS.  Offset (in halves) of element (row r < 16, column k):
 __host__ __device__ __forceinline__ size_t w4a16_xperm_offset(int r, int k) {

@@ -1,5 +1,5 @@
 // EXPERIMENTAL -- not part of libqspec_hip.so.  Measured and rejected variants (DESIGN.md section 4, "Measured and rejected");
-// included into gemm_stream.hip only under -DQS_EXPERIMENTAL (make -C qspec_amd/csrc experimental -> libqspec_hip_experimental.so),
+// included into gemm_stream_f16.hip only under -DQS_EXPERIMENTAL (make -C qspec_amd/csrc experimental -> libqspec_hip_experimental.so),
 // kept with their tests (which select that library through QSPEC_HIP_LIB) for the record.
 
 // ------------------------------------------------------------------ weight prefetch into the Infinity Cache

@@ -1,5 +1,5 @@
 // EXPERIMENTAL -- not part of libqspec_hip.so.  Measured and rejected variants (DESIGN.md section 4, "Measured and rejected");
-// included into gemm_stream.hip only under -DQS_EXPERIMENTAL (make -C qspec_amd/csrc experimental -> libqspec_hip_experimental.so),
+// included into gemm_stream_w4a4.hip only under -DQS_EXPERIMENTAL (make -C qspec_amd/csrc experimental -> libqspec_hip_experimental.so),
 // kept with their tests (which select that library through QSPEC_HIP_LIB) for the record.
 
 // ------------------------------------------------------------------ loader / consumer form ("engine"), M <= 4
@@ -216,11 +216,7 @@ __global__ __launch_bounds__((QS_ENG_NC + 4 + QS_ENG_NE) * 64) void gemm_w4a4_en
             }
             if (EPI == SEPI_GATEUP) {
                 const f16 partner = u2h((uint16_t)__shfl_xor((int)h2u(hv), 8, 64));
-                if (ethread && c < 8) {  // hv = up, partner = gate
-                    const float gt = h2f(partner);
-                    const float act = h2f(f2h(gt / (1.0f + qexpf(-gt))));
-                    a.out[(size_t)m * a.I + tile * 8 + c] = f2h(act * h2f(hv));
-                }
+                if (ethread) stream_epilogue_pair<SEPI_GATEUP>(a, tile, m, c, hv, partner, swn, swn, 0);   // (cf / sf: unused)
             }
             if (ew == 0) QS_ESTAMP(5, ti);
             tile += NE * (int)gridDim.x;
@@ -393,13 +389,8 @@ template <int EPI, int PRO, int NI, int FPT, int R>
 static int launch_engine_inst(const StreamArgs& a, hipStream_t st) {
     const size_t lds = eng_lds_bytes(a.K, R);
     if (lds > 160 * 1024) return -7;
-    static bool attr_set = false;  // per instantiation
     auto kern = gemm_w4a4_engine_kernel<EPI, PRO, NI, FPT, R>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return -8;
-        attr_set = true;
-    }
+    if (const int rc = stream_lds_optin<gemm_w4a4_engine_kernel<EPI, PRO, NI, FPT, R>>(lds, true)) return rc;
     const int grid = a.ntiles < 256 ? a.ntiles : 256;   // one workgroup per CU
     if ((a.ntiles + grid - 1) / grid > (EPI == SEPI_RESID ? 2 : 8) * QS_ENG_NE) return -9;   // scales held per epilogue wave
     hipLaunchKernelGGL(kern, dim3(grid), dim3((QS_ENG_NC + 4 + QS_ENG_NE) * 64), lds, st, a);

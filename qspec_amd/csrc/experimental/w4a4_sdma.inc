@@ -1,5 +1,5 @@
 // EXPERIMENTAL -- not part of libqspec_hip.so.  Measured and rejected variants (DESIGN.md section 4, "Measured and rejected");
-// included into gemm_stream.hip only under -DQS_EXPERIMENTAL (make -C qspec_amd/csrc experimental -> libqspec_hip_experimental.so),
+// included into gemm_stream_w4a4.hip only under -DQS_EXPERIMENTAL (make -C qspec_amd/csrc experimental -> libqspec_hip_experimental.so),
 // kept with their tests (which select that library through QSPEC_HIP_LIB) for the record.
 
 // ------------------------------------------------------------------ self-service LDS-DMA form, M <= 4, K = 4096
@@ -84,13 +84,10 @@ __global__ __launch_bounds__(8 * 64 + 256) void gemm_w4a4_sdma_kernel(StreamArgs
             const float v = ((float)(sum >> 8) * xs_m) * h2f(swn[i]);  // both operands carried a factor 16
             const f16 hv = f2h(v);
             const f16 partner = u2h((uint16_t)__shfl_xor((int)h2u(hv), 8, 64));
-            if (EPI == SEPI_GATEUP) {
-                if (ethread && c < 8) {  // hv = up, partner = gate
-                    const float gt = h2f(partner);
-                    const float act = h2f(f2h(gt / (1.0f + qexpf(-gt))));
-                    a.out[(size_t)m * a.I + tile * 8 + c] = f2h(act * h2f(hv));
-                }
-            } else {   // SEPI_QKV
+            if constexpr (EPI == SEPI_GATEUP) {
+                if (ethread) stream_epilogue_pair<EPI>(a, tile, m, c, hv, partner, cf[i], sf[i], slot_m);
+            } else {   // SEPI_QKV: classic tiles, head size 128, fp16 caches only (the host checks) -- kept as its own text: the
+                       // general tail of stream_common.cuh costs this kernel 2-4 more SGPRs
                 const int head = tile >> 3, o = (tile & 7) * 8 + (c & 7);
                 const int n = head * 128 + (c >> 3) * 64 + o;
                 f16 res = hv;
@@ -187,13 +184,8 @@ template <int EPI, int PRO, int NI, int R>
 static int launch_sdma_inst(const StreamArgs& a, hipStream_t st) {
     const size_t lds = (((size_t)4 * (a.K / 2 + 32) + 64 + 2 * 8 * 256 + 1023) & ~(size_t)1023) + (size_t)R * 32768;
     if (lds > 160 * 1024) return -7;
-    static bool attr_set = false;  // per instantiation
     auto kern = gemm_w4a4_sdma_kernel<EPI, PRO, NI, R>;
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return -8;
-        attr_set = true;
-    }
+    if (const int rc = stream_lds_optin<gemm_w4a4_sdma_kernel<EPI, PRO, NI, R>>(lds, true)) return rc;
     const int grid = a.ntiles < 256 ? a.ntiles : 256;   // one workgroup per CU
     if ((a.ntiles + grid - 1) / grid > (EPI == SEPI_QKV ? 2 : 8)) return -9;   // epilogue operands held per workgroup
     hipLaunchKernelGGL(kern, dim3(grid), dim3(8 * 64 + 256), lds, st, a);

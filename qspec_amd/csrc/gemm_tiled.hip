@@ -8,7 +8,7 @@
 //     (v_mfma_f32_32x32x16_f16: 4 MFMAs of MT token tiles per 16 packed bytes -> the 40 VALU of the dequantiser
 //     ride under 16 * MT matrix instructions).
 //   * Weights HBM -> VGPR, 16 B per lane (lane = weight row + 32 * k-group), 8 K steps (8 KiB per wave) in flight with
-//     the refill-behind-use pipeline of gemm_stream.hip; no load sits behind a branch.
+//     the refill-behind-use pipeline of gemm_stream_w4a4.hip; no load sits behind a branch.
 //   * Activations: [32 MT x 256 k] stages through LDS (coalesced 16-byte loads, chunks XOR-swizzled by the row), double
 //     buffered: the loads of stage p+1 are issued before stage p is consumed.
 //   * grid = (N / 128, ceil(M / (32 MT))); MT in {1, 2, 3, 4} chosen so that the token blocks cover M with little

@@ -490,7 +490,7 @@ __global__ __launch_bounds__(1024) void heads_hadamard_merge_kernel(const float*
 // Thread (wave w, lane): head = 4 w + (lane >> 4), column = lane & 15.  Same merge expression per element and the same
 // butterfly order (head strides 1, 2 across lanes; 4, 8, 16 across the waves through 2 KB of LDS) as the kernel above.
 // AMAX: also leaves max |output| of the workgroup's 512 values in part_amax[t][y] -- the o_proj launch of the draft pass
-// combines the eight maxima of a row and quantises the fp16 row in its own prologue (gemm_stream.hip, PRO_RQ), so the
+// combines the eight maxima of a row and quantises the fp16 row in its own prologue (gemm_stream_w4a4.hip, PRO_RQ), so the
 // eight workgroups of a token need no exchange here either.
 template <bool AMAX>
 __global__ __launch_bounds__(512) void heads_hadamard_merge_spread32_kernel(const float* __restrict__ ws_o,
@@ -581,7 +581,7 @@ __global__ __launch_bounds__(512) void heads_hadamard_merge_spread32_kernel(cons
 // fp32 fma chain over the table), so the same bits -- without the in-kernel split merge of the attention launch (ticket +
 // fences: 6 of its 12 us), without the one-workgroup-per-token transform (17 us for 4 tokens on 4 CUs) and, for the
 // draft pass, without the separate quantiser launch: AMAX leaves max |output| of the workgroup's share in
-// part_amax[t][y] and the row-absmax quantiser runs in the prologue of the o_proj launch (gemm_stream.hip, PRO_RQ).
+// part_amax[t][y] and the row-absmax quantiser runs in the prologue of the o_proj launch (gemm_stream_w4a4.hip, PRO_RQ).
 // Thread (head = tid / 16, column = tid % 16); LDS: y [heads][16] fp32 + the table as fp32.
 template <bool AMAX>
 __global__ __launch_bounds__(1024) void heads_hadamard_mix_merge_spread_kernel(const float* __restrict__ ws_o,

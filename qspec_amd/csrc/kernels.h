@@ -48,7 +48,7 @@ int heads_hadamard_merge(const float* ws, int max_tokens, int n_splits, f16* out
                          float had_scale, float clip, int T, int heads, int d, hipStream_t st, int xp = 0);
 int silu_mul(const f16* gate_up, f16* out, int T, int I, hipStream_t st);
 bool mlp_hadamard_xperm_supported(int T, int I, int K);
-// 17..32 tokens: two fragment-major 16-row tiles, the two-token-tile streaming kernel (gemm_stream.hip: gemm_w4a16_stream2_kernel)
+// 17..32 tokens: two fragment-major 16-row tiles, the two-token-tile streaming kernel (gemm_stream_w4a16.hip: gemm_w4a16_stream2_kernel)
 bool gemm_w4a16_stream32_supported(int M, int N, int K);
 int gemm_w4a16_stream32_partial_slices(int M, int N, int K);
 int gemm_w4a16_stream32_partial(const f16* x, const int8_t* wq, float* part, int M, int N, int K, int S, hipStream_t st);
@@ -84,7 +84,7 @@ int gemm_w4a16_strided(const f16* x, int64_t ldx, const int8_t* wq, int64_t ldw,
 int gemm_f16(const f16* x, const f16* w, f16* out, int M, int N, int K, hipStream_t st);
 int dequant_w4(const int8_t* wq, const f16* ws, f16* out, int N, int K, hipStream_t st);
 
-// gemm_stream.hip: W4A4 for M <= 16 with the activations produced in the prologue.
+// gemm_stream_w4a4.hip: W4A4 for M <= 16 with the activations produced in the prologue.
 // Either (xq, xs) -- packed int4 rows + scales -- or (hidden_in, delta, hidden_out, eps): the residual add +
 // LN-no-gamma + int4 quant of quarot_llama.py:373-388 fused in front of the GEMM (hidden_out != hidden_in).
 struct StreamActs {
@@ -120,7 +120,7 @@ int gemm_w4a4_stream_qkv_rope(const StreamActs& x, const int8_t* wq, const f16* 
 int gemm_w4a4_stream_gate_up_silu(const StreamActs& x, const int8_t* wq, const f16* ws, f16* act, int M, int I, int K,
                                   hipStream_t st);
 
-// W4A16 on the same streaming skeleton (M <= 16, K = 128 * NW * UB for a built (NW, UB))
+// gemm_stream_w4a16.hip: W4A16 on the same streaming skeleton (M <= 16, K = 128 * NW * UB for a built (NW, UB))
 bool gemm_w4a16_stream_supported(int M, int N, int K);
 bool gemm_w4a16_xperm_supported(int M, int K);
 int gemm_w4a16_stream(const f16* x, int64_t ldx, const int8_t* wq, int64_t ldw, const f16* ws, f16* out, int M, int N,
@@ -147,6 +147,7 @@ int gemm_w4a16_tiled(const f16* x, const int8_t* wq, const f16* ws, f16* out, in
 bool gemm_f16_tiled_supported(int M, int N, int K);
 int gemm_f16_tiled(const f16* x, const f16* w, f16* out, int M, int N, int K, hipStream_t st);
 
+// gemm_stream_f16.hip: the lm_head (fp16 x fp16^T) on the same streaming skeleton
 bool gemm_f16_stream_supported(int M, int N, int K);
 int gemm_f16_stream(const f16* x, const f16* w, f16* out, int M, int N, int K, void* part_max, hipStream_t st);
 int gemm_f16_stream_grid(int N);

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void ln_kernel(const f16* x, const f16* __rest
         da[it] = *reinterpret_cast<const f16x4*>(dsrc + (size_t)row * H + it * 1024 + 4 * j);
     }
     if (part) {
-        // delta arrives as S raw fp32 K-slice sums of a W4A16 projection (gemm_stream.hip, SEPI_PARTIAL):
+        // delta arrives as S raw fp32 K-slice sums of a W4A16 projection (gemm_stream_w4a16.hip, SEPI_PARTIAL):
         // delta = h((p_0 + p_1 + ...) * f(sw)), the expression of w4a16_partial_finish_kernel
         f32x4 sum[NI];
         f16x4 w4[NI];
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) void ln_kernel(const f16* x, const f16* __rest
             for (int c = 0; c < 4; c++) da[it][c] = f2h(sum[it][c] * h2f(w4[it][c]));
     }
     if (ipart) {
-        // delta arrives as S raw int32 K-slice sums of a W4A4 projection (gemm_stream.hip, SEPI_IPART): the slices add up
+        // delta arrives as S raw int32 K-slice sums of a W4A4 projection (gemm_stream_w4a4.hip, SEPI_IPART): the slices add up
         // exactly, then the GEMM's own epilogue expression: delta = h((f(i_0 + i_1 + ...) * f(xs[row])) * f(sw[col]))
         typedef int i32x4v __attribute__((ext_vector_type(4)));
         i32x4v isum[NI];
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void ln_kernel(const f16* x, const f16* __rest
     const bool second = (j & 1) != 0;
     const float ql = (second ? amax : 7.0f) / (second ? 7.0f : amax);
     const float s = readlane_f(ql, 0);
-    // |t| <= 7.21 for every finite row (gemm_stream.hip:ln_compute has the bound), so the reference's clamp to [-8, 7]
+    // |t| <= 7.21 for every finite row (gemm_stream_w4a4.hip:ln_compute has the bound), so the reference's clamp to [-8, 7]
     // never acts; round to nearest even by adding 1.5 * 2^23 (+ 8): the low mantissa nibble is q + 8 with zeros above it
     // up to bit 22 -> four nibbles spliced by three shift-or's, one xor turns the offset nibbles into two's complement
 #pragma unroll

@@ -133,7 +133,7 @@ class ForwardPlan:
     form: str        # last_forward_form: "two-tile" | "fragment-major" | "fused" | "unfused"
     w4a4: bool       # draft pass
     fuse: bool       # fused GEMM epilogues (qkv + RoPE + KV write, gate_up + SiLU)
-    ln_fused: bool   # draft: residual add + LN + int4 quant in the qkv / gate_up prologues (gemm_stream.hip), no hand-over
+    ln_fused: bool   # draft: residual add + LN + int4 quant in the qkv / gate_up prologues (gemm_stream_w4a4.hip), no hand-over
     hq: bool         # ... and the head transform's quantiser in o_proj's prologue
     xp: bool         # verify, <= 16 tokens: fragment-major activation tiles
     xp32: bool       # verify, 17..32 tokens: two tiles, the two-token-tile streaming kernel

@@ -42,7 +42,7 @@ _WS_KINDS = {
     "sample":  ("qspec_sample_workspace_bytes", True, True, _U8),             # histogram of sample_top_k_top_p
 }
 # int32 index of the sticky error word of the kinds that carry one; mirrors QS_XWG_ERR_WORD (csrc/hadamard.hip) and
-# the hand-off kernel's `sync[31]` (csrc/gemm_stream.hip; "int32 word 31" in include/qspec_hip.h)
+# the hand-off kernel's `sync[31]` (csrc/gemm_stream_w4a4.hip; "int32 word 31" in include/qspec_hip.h)
 _ERROR_WORD = {"xwg": 0, "ln": 31}
 _workspaces = {}    # (kind, device.type, device.index, stream[, rows]) -> tensor
 _tls = threading.local()    # .no_handoffs: how many no_handoffs() blocks this thread is inside

@@ -4,7 +4,7 @@ Python, and a case list that reaches every row of that rule -- the GEMM counterp
 Rows (what `route` returns; the product build's defaults: stream cap 256, QSPEC_TILED_MIN_M 17, head LDS-DMA on, the
 W4A16 workspace always passed):
   W4A4  rowwise_scaled_linear_cutlass_s4s4_unified
-    a4.longk        gemm_stream.hip gemm_w4a4_longk_kernel           no bias, M 1..16, K = 28672
+    a4.longk        gemm_stream_w4a4.hip gemm_w4a4_longk_kernel           no bias, M 1..16, K = 28672
     a4.stream1      gemm_w4a4_stream_kernel, one token tile          no bias, M 1..16, K in stream_shape
     a4.stream2      gemm_w4a4_stream_kernel, two token tiles         no bias, M 17..32, K in stream_shape with NW >= 8
     a4.gen{1,2,4}   gemm.hip gemm_w4a4_kernel<MT>                    the rest, one launch per 64-row pass
@@ -42,16 +42,16 @@ import numpy as np
 
 # ------------------------------------------------------------------ constants of the product build
 
-STREAM_CAP = 256            # gemm_stream.hip stream_cap()
+STREAM_CAP = 256            # stream_common.cuh stream_cap()
 TILED_MIN_M = 17            # capi.hip tiled_min_m()
 W16_CNT_BYTES = 8192        # gemm.hip QS_W16_CNT_SLOTS * sizeof(int): the ticket counters at the front of the workspace
 W16_CNT_SLOTS = 2048
 W16_PART_BYTES = 32 * 1024 * 1024
 W16_WS_BYTES = W16_CNT_BYTES + W16_PART_BYTES
 
-# gemm_stream.hip stream_shape(): K / 128 = NW * UB
+# gemm_stream_w4a4.hip QS_W4A4_SHAPES: K / 128 = NW * UB
 A4_STREAM_SHAPES = ((8, 4), (16, 7), (8, 8), (8, 5), (4, 4), (4, 2), (4, 7), (12, 9), (4, 11))
-# gemm_stream.hip stream16_shape()
+# gemm_stream_w4a16.hip QS_W4A16_SHAPES16
 W16_STREAM_SHAPES = ((8, 4), (8, 8), (8, 5), (4, 4), (4, 2), (8, 7), (4, 7), (4, 1), (4, 9), (4, 11))
 F16_STREAM = {4096: (8, 16), 2048: (8, 8), 1024: (4, 8), 5120: (8, 20)}   # gemm_f16_stream(); 8192 is the longk kernel
 
@@ -150,7 +150,7 @@ def w16_stream_shape(K):
 
 
 def a4_stream_lds(M, K, NW, MT):
-    """gemm_stream.hip stream_lds_bytes() for the (xq, xs) prologue (no staged rows)."""
+    """gemm_stream_w4a4.hip stream_lds_bytes() for the (xq, xs) prologue (no staged rows)."""
     NG, RB = NW // 4, (4 if NW == 4 else (2 if NW == 8 else 1))
     return 64 + 2 * NW * MT * 1024 + MT * 1024 + 3 * NG * RB * 32 * 4
 

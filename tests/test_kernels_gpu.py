@@ -450,6 +450,57 @@ def test_ln_prologue_gemms_equal_ln_then_gemm(ops, oracle, M, K, with_delta, han
     assert torch.equal(act.view(torch.int16), act_ref.view(torch.int16))
 
 
+@pytest.mark.parametrize("residual", [False, True], ids=["pure", "residual"])
+@pytest.mark.parametrize("M,handoff", [(3, False), (6, False), (6, True)], ids=["split", "unsplit", "handoff"])
+@pytest.mark.parametrize("K", [1024, 2048, 4096, 5120, 8192])
+def test_ln_prologue_every_dispatch_row(ops, oracle, K, M, handoff, residual, monkeypatch):
+    """Every row of the norm-prologue dispatch (gemm_stream_w4a4.hip: stream_form() x QS_LN_SHAPES), bit for bit against
+    the separate LN kernel followed by the (q, scale) GEMM entries: each K as the split form (M = 3; K = 8192 has none
+    and falls through to the unsplit one), as the unsplit form (M = 6) and with the producer hand-off (M = 6), each as
+    the pure norm of hidden_in (no delta, nothing written back) and as the residual form (delta added, stream written
+    by workgroup 0).  16 weight rows per tile: 64 qkv and 32 gate_up tiles per launch."""
+    monkeypatch.setattr(ops, "LN_HANDOFF", handoff)
+    monkeypatch.setattr(ops, "LN_HANDOFF_MIN_M", 1)
+    rng = np.random.default_rng(K + 31 * M + 2 * handoff + residual)
+    nq, nkv, d, bs, I = 4, 2, 128, 16, 256
+    N = (nq + 2 * nkv) * d
+    hidden = dev(rand_hidden(rng, M, K))
+    delta = dev(rand_hidden(rng, M, K, 0.3)) if residual else None
+    wq = dev(oracle.pack_i4(rand_w4(rng, N, K)))
+    ws = dev((rng.random(N) * 0.01 + 0.001).astype(np.float16))
+    wg = dev(oracle.pack_i4(rand_w4(rng, 2 * I, K)))
+    wgs = dev((rng.random(2 * I) * 0.01 + 0.001).astype(np.float16))
+    cs = dev(oracle.make_cos_sin_cache(d, 2048, 10000.0))
+    pos = dev(rng.integers(0, 2048, M).astype(np.int64))
+    slots_np = rng.permutation(64 * bs)[:M].astype(np.int64)
+    slots_np[1] = -1
+    slots = dev(slots_np)
+    # reference: LN kernel, then the GEMM entries on its (q, scale)
+    q = torch.empty(M, K // 2, dtype=torch.int8, device=DEV)
+    sc = torch.empty(M, dtype=torch.float16, device=DEV)
+    h_ref = torch.empty_like(hidden) if residual else None
+    ops.add_rms_norm_i4(q, sc, h_ref, hidden, delta, 1e-5)
+    qkv_ref = torch.empty(M, N, dtype=torch.float16, device=DEV)
+    kc0 = torch.zeros(64, bs, nkv, d, dtype=torch.float16, device=DEV); vc0 = torch.zeros_like(kc0)
+    ops.qkv_rope_linear(q, sc, wq, ws, qkv_ref, pos, cs, kc0, vc0, slots, nq, nkv, d)
+    act_ref = ops.gate_up_silu_linear(q, sc, wg, wgs, torch.empty(M, I, dtype=torch.float16, device=DEV))
+    # fused
+    assert ops.ln_linear_s4s4_supported(M, N, K)
+    h1 = torch.full_like(hidden, float("nan")) if residual else None
+    h2 = torch.full_like(hidden, float("nan")) if residual else None
+    qkv = torch.empty_like(qkv_ref)
+    kc1 = torch.zeros_like(kc0); vc1 = torch.zeros_like(kc0)
+    ops.ln_qkv_rope_linear(hidden, delta, h1, 1e-5, wq, ws, qkv, pos, cs, kc1, vc1, slots, nq, nkv, d)
+    act = ops.ln_gate_up_silu_linear(hidden, delta, h2, 1e-5, wg, wgs, torch.empty(M, I, dtype=torch.float16, device=DEV))
+    torch.cuda.synchronize()
+    if residual:   # (pure norm: nothing is written back)
+        assert torch.equal(h1.view(torch.int16), h_ref.view(torch.int16))
+        assert torch.equal(h2.view(torch.int16), h_ref.view(torch.int16))
+    assert torch.equal(qkv.view(torch.int16), qkv_ref.view(torch.int16))
+    assert torch.equal(kc1, kc0) and torch.equal(vc1, vc0)
+    assert torch.equal(act.view(torch.int16), act_ref.view(torch.int16))
+
+
 @pytest.mark.parametrize("handoff", [False, True])
 def test_ln_prologue_edge_rows(ops, oracle, handoff, monkeypatch):
     """Edge rows through the fused norm prologue: all-zero (amax floor 1e-6), constant, tiny, near-overflow, exact
@@ -484,7 +535,7 @@ def test_ln_prologue_edge_rows(ops, oracle, handoff, monkeypatch):
 @pytest.mark.parametrize("M", [4, 3, 16])
 def test_ln_prologue_full_layer_shapes_with_lds_prefetch(ops, oracle, M, monkeypatch):
     """Llama-3-8B layer shapes: several tiles per workgroup, so the tiles behind the first one are brought into LDS
-    by LDS-DMA underneath the norm (gemm_stream.hip).  Against the separate LN kernel + the plain GEMM entries."""
+    by LDS-DMA underneath the norm (gemm_stream_w4a4.hip).  Against the separate LN kernel + the plain GEMM entries."""
     monkeypatch.setattr(ops, "LN_HANDOFF", False)
     rng = np.random.default_rng(M)
     K, nq, nkv, d, bs, I = 4096, 32, 8, 128, 16, 14336
@@ -1569,7 +1620,7 @@ def test_attention_waves_kernel_dev_forms(switch, kexpr):
     """Forms that are built, measured and off against the same oracle comparisons as the
     defaults, re-run in a child process with the switch on (the library reads it once per process):
     paged_attention_waves_kernel's general per-lane table lookup instead of the two wave-uniform entries per slice, and its
-    eight-wave form; the levelled qkv tiling (twelve RoPE pairs per workgroup, gemm_stream.hip:qkv_pair) in the W4A16 and
+    eight-wave form; the levelled qkv tiling (twelve RoPE pairs per workgroup, stream_common.cuh:qkv_pair) in the W4A16 and
     W4A4 qkv + RoPE + KV-write launches of this file."""
     import os
     import subprocess
