@@ -117,12 +117,20 @@ __device__ __forceinline__ float aexp(float x) { return __builtin_amdgcn_exp2f(x
 // instructions: q0 = x * r, q1 = q0 + (x - q0 * s) * r with r = 1 / s correctly rounded (once per row).  The fp16
 // rounding of q1 equals the fp16 rounding of the correctly rounded fp32 quotient for EVERY pair of finite fp16 x and
 // positive finite fp16 s -- checked exhaustively (2^30 pairs) by tests/test_oracle_golden.py::test_three_op_fp16_division;
-// s = 0 (all-zero row) gives NaN like 0 / 0 does.  (An IEEE fp32 division is ~11 instructions.)
+// s = 0: div3_rcp below.  (An IEEE fp32 division is ~11 instructions.)
 __device__ __forceinline__ float div3_h(float x, float r, float s) {
     const float q0 = x * r;
     const float rem = __builtin_fmaf(-q0, s, x);
     return __builtin_fmaf(rem, r, q0);
 }
+// The r a quantiser hands to div3_h for its row's scale s (once per row): 1 / s, and 2^41 for s = 0.  A scale of 0 is not
+// only the all-zero row: scale = h(h(amax / 7) h(clip)) also rounds to 0 for a row maximum up to 3.5 * 2^-24 at clip 1, for
+// larger rows at a smaller clip and for every row at clip 0, while the row still holds nonzero values.  h(x / scale) is then
+// x / 0 = +-inf, which clamps to +7 / -8 (quant.cu:147 __hdiv, the oracle), and 0 / 0 = NaN -> 0.  With r = inf div3_h
+// returns NaN -> 0 for every x.  With r = 2^41 and s = 0 it gives q0 = x 2^41, rem = x, q1 = 2 x 2^41: finite for every finite
+// fp16 x (|x| < 2^16), at least 2^18 in magnitude for every nonzero one (|x| >= 2^-24), so its fp16 rounding is the +-inf of
+// the quotient, and 0 for x = 0.
+__device__ __forceinline__ float div3_rcp(float s) { return s == 0.0f ? 0x1p41f : 1.0f / s; }
 
 __device__ __forceinline__ int rni_sat(float v, int lo, int hi) {
     if (v != v) return 0;

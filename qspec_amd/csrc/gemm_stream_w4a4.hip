@@ -715,7 +715,7 @@ __global__ __launch_bounds__(NW * 64 + (pro_split<PRO>() ? 256 : 0) + (DMA > 0 ?
         pv = dpp_max_xor<4>(pv);
         // scale = h(h(amax / 7) * h(clip)) and its correctly rounded reciprocal, lane-parallel (lane 8 r works on row r)
         const f16 scl = f2h(h2f(f2h(pv / 7.0f)) * h2f(f2h(a.clip)));
-        const float scfl = h2f(scl), rcfl = 1.0f / scfl;
+        const float scfl = h2f(scl), rcfl = div3_rcp(scfl);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const float scf = readlane_f(scfl, 8 * i), rcf = readlane_f(rcfl, 8 * i);
@@ -723,8 +723,8 @@ __global__ __launch_bounds__(NW * 64 + (pro_split<PRO>() ? 256 : 0) + (DMA > 0 ?
             for (int cc = 0; cc < CPT; cc++) {
                 const f16x8 x8 = __builtin_bit_cast(f16x8, xr[i][cc]);
                 // rni_sat(h(x / scale), -8, 7) as: clamp, then round to nearest even by adding 1.5 * 2^23 -- the two's
-                // complement integer is the low mantissa bits.  (The quotient of finite values by a non-zero scale is never
-                // NaN; an all-zero row has scale 0, every quotient NaN and the reference's 0 for it: selected per row below.)
+                // complement integer is the low mantissa bits.  (No quotient is NaN: with a scale of 0 div3_rcp makes div3_h
+                // give +-inf for x != 0, which clamps to +7 / -8 as the reference's x / 0 does, and 0 for x = 0.)
                 u32 pk = 0;
 #pragma unroll
                 for (int c = 0; c < 8; c++) {
@@ -734,7 +734,6 @@ __global__ __launch_bounds__(NW * 64 + (pro_split<PRO>() ? 256 : 0) + (DMA > 0 ?
                     asm("" : "+v"(mg));
                     pk |= (__builtin_bit_cast(u32, mg) & 0xFu) << (4 * c);
                 }
-                if (scf == 0.0f) pk = 0;   // uniform
                 const int ch = tid + cc * NW * 64;
                 if (i < a.M && (CPT * NW * 64 == NCH || ch < NCH)) *reinterpret_cast<u32*>(xq_lds + (size_t)i * RS + 4 * ch) = pk;
             }

@@ -199,7 +199,7 @@ __global__ __launch_bounds__(128) void heads_hadamard_kernel(const f16* __restri
     }
     const f16 sc = f2h(h2f(f2h(amax / 7.0f)) * h2f(f2h(clip)));
     const float scf = h2f(sc);
-    const float rcf = 1.0f / scf;   // correctly rounded reciprocal for div3_h
+    const float rcf = div3_rcp(scf);   // correctly rounded reciprocal for div3_h
     if (j == 0) scale[t] = sc;
     if (!act) return;
 #pragma unroll
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(NH * 8) void heads_hadamard_wide_kernel(const f16* 
     for (int j = 1; j < HG; j++) amax = fmaxf(amax, red[j]);
     const f16 sc = f2h(h2f(f2h(amax / 7.0f)) * h2f(f2h(clip)));
     const float scf = h2f(sc);
-    const float rcf = 1.0f / scf;   // correctly rounded reciprocal for div3_h
+    const float rcf = div3_rcp(scf);   // correctly rounded reciprocal for div3_h
     if (tid == 0) scale[t] = sc;
 #pragma unroll
     for (int h = 0; h < 8; h++) {
@@ -472,7 +472,7 @@ __global__ __launch_bounds__(1024) void heads_hadamard_merge_kernel(const float*
     for (int j = 1; j < HG; j++) amax = fmaxf(amax, red[j]);
     const f16 sc = f2h(h2f(f2h(amax / 7.0f)) * h2f(f2h(clip)));
     const float scf = h2f(sc);
-    const float rcf = 1.0f / scf;   // correctly rounded reciprocal for div3_h
+    const float rcf = div3_rcp(scf);   // correctly rounded reciprocal for div3_h
     if (tid == 0) scale[t] = sc;
 #pragma unroll
     for (int h = 0; h < 8; h++) {
@@ -793,7 +793,7 @@ __global__ __launch_bounds__(512) void heads_hadamard_merge_cols_kernel(const fl
     }
     const f16 sc = f2h(h2f(f2h(amax / 7.0f)) * h2f(f2h(clip)));
     const float scf = h2f(sc);
-    const float rcf = 1.0f / scf;
+    const float rcf = div3_rcp(scf);
     if (j == 0) scale[t] = sc;
     if (!act) return;
 #pragma unroll
@@ -1171,7 +1171,7 @@ __global__ __launch_bounds__(QS_SMH_THREADS) void silu_mul_hadamard_kernel(const
         amax = xwg_row_amax(red, NW, xgen, t, b, NB, xws, reinterpret_cast<float*>(zlds) + 1024);
         const f16 sc = f2h(h2f(f2h(amax / 7.0f)) * h2f(f2h(clip)));
         const float scf = h2f(sc);
-        const float rcf = 1.0f / scf;
+        const float rcf = div3_rcp(scf);
         if (tid == 0 && b == 0) scale[t] = sc;
         // one byte per thread -> LDS -> 16-byte stores (a row's block is CB / 2 contiguous bytes of the packed row)
         unsigned char* qb = reinterpret_cast<unsigned char*>(zlds);
@@ -1218,8 +1218,11 @@ __global__ __launch_bounds__(QS_SMH_THREADS) void silu_mul_hadamard_kernel(const
                 // in k order is unchanged.  k in quads outside, the thread's KH/4 rows inside: 2 x KH/4 accumulators.
                 typedef float f32x2 __attribute__((ext_vector_type(2)));
                 constexpr int RQ = KH / 4;                     // rows per thread
-                const int j4 = tid % (P / 4), rq = tid / (P / 4);
-                if (rq < 4) {
+                // P / 4 threads per row group: all four groups at once up to P = 1024; P = 2048 (had12 x H2048) has 512
+                // threads per group, so a thread takes groups rq and rq + 2
+                constexpr int RQG = NT / (P / 4);
+                const int j4 = tid % (P / 4);
+                for (int rq = tid / (P / 4); rq < 4; rq += RQG) {
                     f32x2 a0[RQ], a1[RQ];
 #pragma unroll
                     for (int r = 0; r < RQ; r++) a0[r] = a1[r] = f32x2{0.0f, 0.0f};
@@ -1325,7 +1328,7 @@ __global__ __launch_bounds__(QS_SMH_THREADS) void silu_mul_hadamard_kernel(const
     for (int w = 1; w < NW; w++) amax = fmaxf(amax, red[w]);
     const f16 sc = f2h(h2f(f2h(amax / 7.0f)) * h2f(f2h(clip)));
     const float scf = h2f(sc);
-    const float rcf = 1.0f / scf;   // correctly rounded reciprocal for div3_h
+    const float rcf = div3_rcp(scf);   // correctly rounded reciprocal for div3_h
     if (tid == 0) scale[t] = sc;
     for (int i = tid; i < nvec; i += NT) {
         f16x8 a = *reinterpret_cast<const f16x8*>(zsrc + 8 * i);
@@ -1360,11 +1363,13 @@ static int smh_spread(int T, int P, int K, int pre_activated, const void* xws) {
     return T * nb <= 256 ? nb : 1;     // every workgroup of a token resident: at most one workgroup per CU
 }
 
-// the forms that can write the fragment-major tile: the spread ones (a workspace is given), at most 16 tokens
+// the shapes at which mlp_hadamard(xp) writes the fragment-major tile(s) for the GEMM that reads them: the spread forms (up to
+// 32 tokens) and, at 17..32 tokens, the one-workgroup form -- within the LDS cap that silu_mul_hadamard refuses with -2
 bool mlp_hadamard_xperm_supported(int T, int I, int K) {
     if (T < 1 || T > 32 || K < 1 || K > 172 || I % K) return false;
     const int P = I / K;
     if (P & (P - 1)) return false;
+    if (64 + (size_t)I * 2 * (K > 1 ? 2 : 1) + (K > 1 ? (size_t)K * K * 4 : 0) > 160 * 1024 - 64) return false;   // silu_mul_hadamard's LDS cap (-2)
     static const int dummy = 0;
     if (smh_spread(T, P, K, 1, &dummy) > 1) return true;      // the spread forms
     return T > 16 && (P == 128 || P == 256 || P == 512 || P == 1024 || P == 2048) && I % 128 == 0;   // 17..32 tokens: also the one-workgroup form

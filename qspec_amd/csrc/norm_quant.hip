@@ -333,7 +333,7 @@ __global__ __launch_bounds__(256) void rowabsmax_quant_kernel(const f16* __restr
     amax = block_max_256(amax, red);
     const f16 sc = f2h(h2f(f2h(amax / 7.0f)) * h2f(f2h(clip)));
     const float scf = h2f(sc);
-    const float rcf = 1.0f / scf;   // correctly rounded reciprocal for div3_h
+    const float rcf = div3_rcp(scf);   // correctly rounded reciprocal for div3_h
     if (j == 0) scale[row] = sc;
     int8_t* qr = q + (size_t)row * (K / 2);
     for (int i = j; i < nvec; i += 256) {
