@@ -287,7 +287,7 @@ int qspec_rope_kv_write(const int64_t* positions, qspec_half* qkv, const qspec_h
  * out == NULL: the context splits are NOT merged; their partials (o, m, l) stay in the workspace for
  * qspec_heads_hadamard_merged, which merges them in front of the head transform (the launch boundary then is the
  * hand-off between the split workgroups and no ticket / fence is needed).
- * Three kernels sit behind this entry (attention.hip), chosen from the shape alone: 16-row workgroups walking 128-key
+ * Three kernels sit behind this entry (attention.hip: attn_form), chosen from the shape alone: 16-row workgroups walking 128-key
  * chunks (decode / verify, splits of at most one chunk; also every out != NULL call with n_splits > 1); the same grid
  * with the keys over the waves of a workgroup (out == NULL and block_tables wide enough for splits longer than 128
  * keys); 64-row flash-style workgroups for prompt-sized queries (n_splits == 1, max_q_len * num_heads / num_kv_heads

@@ -288,4 +288,18 @@ __device__ __forceinline__ f16x8 dequant_s4x8_bitop(u32 p) {
     return f16x8{h0[0], h0[1], h1[0], h1[1], h2[0], h2[1], h3[0], h3[1]};
 }
 
+// ---- host side
+// Dynamic LDS beyond the 64 KiB a kernel gets unasked: opt in, once per kernel (one `static` per KERN) and again only when
+// a launch needs more than any before it.  first_use: the kernel's LDS size is fixed and always above 64 KiB -- set it
+// on the first launch without looking at the size.  0, or -8 when the runtime refuses.
+template <auto KERN>
+static int lds_optin(size_t lds, bool first_use = false) {
+    static size_t attr_set = 0;
+    if (first_use ? attr_set != 0 : (lds <= 64 * 1024 || lds <= attr_set)) return 0;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -8;
+    attr_set = lds;
+    return 0;
+}
+
 }  // namespace qspec

@@ -390,7 +390,7 @@ static int launch_engine_inst(const StreamArgs& a, hipStream_t st) {
     const size_t lds = eng_lds_bytes(a.K, R);
     if (lds > 160 * 1024) return -7;
     auto kern = gemm_w4a4_engine_kernel<EPI, PRO, NI, FPT, R>;
-    if (const int rc = stream_lds_optin<gemm_w4a4_engine_kernel<EPI, PRO, NI, FPT, R>>(lds, true)) return rc;
+    if (const int rc = lds_optin<gemm_w4a4_engine_kernel<EPI, PRO, NI, FPT, R>>(lds, true)) return rc;
     const int grid = a.ntiles < 256 ? a.ntiles : 256;   // one workgroup per CU
     if ((a.ntiles + grid - 1) / grid > (EPI == SEPI_RESID ? 2 : 8) * QS_ENG_NE) return -9;   // scales held per epilogue wave
     hipLaunchKernelGGL(kern, dim3(grid), dim3((QS_ENG_NC + 4 + QS_ENG_NE) * 64), lds, st, a);

@@ -185,7 +185,7 @@ static int launch_sdma_inst(const StreamArgs& a, hipStream_t st) {
     const size_t lds = (((size_t)4 * (a.K / 2 + 32) + 64 + 2 * 8 * 256 + 1023) & ~(size_t)1023) + (size_t)R * 32768;
     if (lds > 160 * 1024) return -7;
     auto kern = gemm_w4a4_sdma_kernel<EPI, PRO, NI, R>;
-    if (const int rc = stream_lds_optin<gemm_w4a4_sdma_kernel<EPI, PRO, NI, R>>(lds, true)) return rc;
+    if (const int rc = lds_optin<gemm_w4a4_sdma_kernel<EPI, PRO, NI, R>>(lds, true)) return rc;
     const int grid = a.ntiles < 256 ? a.ntiles : 256;   // one workgroup per CU
     if ((a.ntiles + grid - 1) / grid > (EPI == SEPI_QKV ? 2 : 8)) return -9;   // epilogue operands held per workgroup
     hipLaunchKernelGGL(kern, dim3(grid), dim3(8 * 64 + 256), lds, st, a);

@@ -496,12 +496,12 @@ static int gemm_f16_sdma_launch(const f16* x, const f16* w, f16* out, int M, int
                                 hipStream_t st) {
     if (M > 16) {   // two token tiles: gemm_f16_sdma2_kernel
         const size_t lds = (size_t)8 * 2 * 1024 + (size_t)8 * 4 * 4096;
-        if (const int rc = stream_lds_optin<gemm_f16_sdma2_kernel>(lds, true)) return rc;
+        if (const int rc = lds_optin<gemm_f16_sdma2_kernel>(lds, true)) return rc;
         hipLaunchKernelGGL(gemm_f16_sdma2_kernel, dim3(grid), dim3(8 * 64), lds, st, x, w, out, M, N, ntiles, pm);
         return 0;
     }
     const size_t lds = (size_t)2 * 8 * 1024 + (size_t)8 * 4 * 4096;
-    if (const int rc = stream_lds_optin<gemm_f16_sdma_kernel<1>>(lds, true)) return rc;
+    if (const int rc = lds_optin<gemm_f16_sdma_kernel<1>>(lds, true)) return rc;
     hipLaunchKernelGGL(gemm_f16_sdma_kernel<1>, dim3(grid), dim3(12 * 64), lds, st, x, w, out, M, N, ntiles, pm);
     return 0;
 }

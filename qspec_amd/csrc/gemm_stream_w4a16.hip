@@ -375,7 +375,7 @@ static int launch_stream32_inst(const StreamArgs& a, hipStream_t st) {
     const int cap = slices > 1 ? (stream_cap() / slices > 0 ? stream_cap() / slices : 1) : stream_cap();   // one workgroup per CU in all
     const int grid = stream_grid(a.ntiles, cap), per = a.ntiles > cap ? (a.ntiles + cap - 1) / cap : 1;   // tiles per workgroup
     const size_t lds = (size_t)2 * 8 * 512 * 4 + 2 * 512 * 2 + (NB > 1 ? (size_t)per * 2048 : 0);
-    if (const int rc = stream_lds_optin<gemm_w4a16_stream2_kernel<EPI, 8, UB, NB>>(lds)) return rc;
+    if (const int rc = lds_optin<gemm_w4a16_stream2_kernel<EPI, 8, UB, NB>>(lds)) return rc;
     hipLaunchKernelGGL((gemm_w4a16_stream2_kernel<EPI, 8, UB, NB>), dim3(grid, slices), dim3(8 * 64), lds, st, a);
     return 0;
 }
@@ -444,7 +444,7 @@ static bool stream16_shape(int K, bool* xperm = nullptr) {
 template <int EPI, int NW, int UB, bool XPERM>
 static int launch_stream16_inst(const StreamArgs& a, hipStream_t st) {
     const size_t lds = (size_t)2 * NW * 1024 + 1024 + (size_t)2 * 16 * NW * 512;   // reduction + activation staging
-    if (const int rc = stream_lds_optin<gemm_w4a16_stream_kernel<EPI, NW, UB, false>>(lds)) return rc;
+    if (const int rc = lds_optin<gemm_w4a16_stream_kernel<EPI, NW, UB, false>>(lds)) return rc;
     const int cap = stream_cap();
     int grid = stream_grid(a.ntiles, cap);
     const int slices = EPI == SEPI_PARTIAL ? a.nq : 1;   // (nq carries the slice count for SEPI_PARTIAL)

@@ -1113,7 +1113,7 @@ template <int EPI, int PRO, int NW, int UB, int NI, int MT = 1, int DMA = 0>
 static int launch_stream_inst(const StreamArgs& a, hipStream_t st) {
     const size_t lds = stream_lds_bytes(a.M, a.K, NW, PRO != PRO_Q, MT) + (DMA > 0 ? 1024 + (size_t)DMA * 32768 : 0);
     if (lds > 160 * 1024) return -7;
-    if (const int rc = stream_lds_optin<gemm_w4a4_stream_kernel<EPI, PRO, NW, UB, NI, MT, DMA>>(lds)) return rc;
+    if (const int rc = lds_optin<gemm_w4a4_stream_kernel<EPI, PRO, NW, UB, NI, MT, DMA>>(lds)) return rc;
     int cap = stream_cap();
     if (PRO == PRO_LNH && cap > 256) cap = 256;   // the fence-free hand-off is calibrated for one workgroup per CU
     const int slices = EPI == SEPI_IPART ? a.nq : 1;   // (nq carries the slice count for SEPI_IPART)

@@ -16,8 +16,7 @@
 // one kernel that reads the producer's layout directly.
 #include <stdlib.h>
 
-#include "common.cuh"
-#include "kernels.h"
+#include "attention_common.cuh"
 
 namespace qspec {
 
@@ -312,9 +311,9 @@ __global__ __launch_bounds__(NH * 8) void heads_hadamard_wide_kernel(const f16* 
 }
 
 // heads_hadamard_wide_kernel with the split merge of the attention kernel in front of it: the attention launch
-// (attention.hip, merge = 0) leaves per-split partials o [T, NH, S, 128] and (m, l) [T, NH, S, 2] in its workspace and
+// (attention_decode.hip, merge = 0) leaves per-split partials o [T, NH, S, 128] and (m, l) [T, NH, S, 2] in its workspace and
 // this kernel combines them -- out = sum_s w_s o_s / sum_s w_s l_s, w_s = e^(m_s - M), splits in order, the same
-// expression as attention.hip's in-kernel merge, rounded to fp16 exactly where flash-attn returns fp16 -- before the
+// expression as the chunk kernel's in-kernel merge (merge_weight, attention_common.cuh), rounded to fp16 exactly where flash-attn returns fp16 -- before the
 // head transform.  The launch boundary replaces the release / ticket / acquire hand-off (6 of the kernel's 12 us).
 // Thread (head = tid / 8, 16 columns) merges with 16-byte loads, all issued up front; the merged row goes through
 // LDS to the Hadamard thread mapping.
@@ -357,7 +356,7 @@ __global__ __launch_bounds__(1024) void heads_hadamard_merge_kernel(const float*
 #pragma unroll
                 for (int v4 = 0; v4 < CP / 4; v4++) o[s2][v4] = *reinterpret_cast<const f32x4*>(ob + (size_t)sc * D + v4 * 4);
             }
-            if (s0 == 0) {   // M over ALL splits first (as attention.hip does): from the registers just loaded;
+            if (s0 == 0) {   // M over ALL splits first (as the chunk kernel's merge does): from the registers just loaded;
                              // only splits beyond the first trip (S > 8, long contexts) are re-read
 #pragma unroll
                 for (int s2 = 0; s2 < SMAX; s2++) M = fmaxf(M, s2 < S ? ml[s2].x : -__builtin_inff());
@@ -367,7 +366,7 @@ __global__ __launch_bounds__(1024) void heads_hadamard_merge_kernel(const float*
             for (int s2 = 0; s2 < SMAX; s2++) {
                 if (s0 + s2 < S) {
                     const float m = ml[s2].x;
-                    const float w = m == -__builtin_inff() ? 0.0f : aexp(m - M);   // = attention.hip's own merge
+                    const float w = merge_weight(m, M);
                     den = __builtin_fmaf(w, ml[s2].y, den);
 #pragma unroll
                     for (int v4 = 0; v4 < CP / 4; v4++)
@@ -524,7 +523,7 @@ __global__ __launch_bounds__(512) void heads_hadamard_merge_spread32_kernel(cons
         for (int s2 = 0; s2 < SMAX; s2++) {
             if (s0 + s2 < S) {
                 const float m = ml[s2].x;
-                const float wgt = m == -__builtin_inff() ? 0.0f : aexp(m - M);
+                const float wgt = merge_weight(m, M);
                 den = __builtin_fmaf(wgt, ml[s2].y, den);
                 num = __builtin_fmaf(wgt, o[s2], num);
             }
@@ -621,7 +620,7 @@ __global__ __launch_bounds__(1024) void heads_hadamard_mix_merge_spread_kernel(c
         for (int s2 = 0; s2 < SMAX; s2++) {
             if (s0 + s2 < S) {
                 const float m = ml[s2].x;
-                const float wgt = m == -__builtin_inff() ? 0.0f : aexp(m - M);
+                const float wgt = merge_weight(m, M);
                 den = __builtin_fmaf(wgt, ml[s2].y, den);
                 num = __builtin_fmaf(wgt, o[s2], num);
             }
@@ -674,8 +673,8 @@ int heads_hadamard_mix_merge_spread(const float* ws, int max_tokens, int n_split
     if (T == 0) return 0;
     if (xp && (part_amax != nullptr || T > 32)) return -1;
     if (!heads_hadamard_mix_merge_spread_supported(T, heads, d, K) || n_splits < 1 || T > max_tokens) return -1;
-    const float* ws_o = ws + paged_attention_ws_o_offset();
-    const float* ws_ml = ws + paged_attention_ws_ml_offset(max_tokens, heads, d, n_splits);
+    const AttnWs w = attn_ws(ws, max_tokens, heads, d, n_splits);
+    const float *ws_o = w.o, *ws_ml = w.ml;
     const int threads = ((heads * 16 + 63) / 64) * 64;
     const size_t lds = ((size_t)heads * 16 + (size_t)K * K + 16) * sizeof(float);
     if (part_amax)
@@ -687,7 +686,7 @@ int heads_hadamard_mix_merge_spread(const float* ws, int max_tokens, int n_split
     return 0;
 }
 
-// heads_hadamard_kernel with the split merge of the generic-head-size attention kernel (attention.hip:
+// heads_hadamard_kernel with the split merge of the generic-head-size attention kernel (attention_generic.hip:
 // paged_attention_generic_vec_kernel, head sizes other than 128 -- TinyLlama's 64) in front of it: 512 threads merge
 // (head, four columns) items -- out = h(sum_s w_s o_s / sum_s w_s l_s), w_s = e^(m_s - M), splits in order: the expression of
 // paged_attention_generic_merge_kernel, so the same fp16 rows -- into LDS, then the first d / 2 lanes run
@@ -726,7 +725,7 @@ __global__ __launch_bounds__(512) void heads_hadamard_merge_cols_kernel(const fl
 #pragma unroll
         for (int s2 = 0; s2 < SMAX; s2++) {
             if (s2 < S) {
-                const float w = ml[s2].x == -__builtin_inff() ? 0.0f : aexp(ml[s2].x - M);
+                const float w = merge_weight(ml[s2].x, M);
                 den = __builtin_fmaf(w, ml[s2].y, den);
 #pragma unroll
                 for (int e = 0; e < 4; e++) num[e] = __builtin_fmaf(w, o[s2][e], num[e]);
@@ -812,8 +811,8 @@ int heads_hadamard_merge(const float* ws, int max_tokens, int n_splits, f16* out
     if (d != 128) {   // generic head sizes (TinyLlama: 32 heads of 64): partials of paged_attention_generic_vec_kernel
         if (heads != 32 || d % 8 || d < 8 || d > 256 || n_splits < 1 || T > max_tokens) return -1;
         const int S = paged_attention_generic_splits(n_splits);
-        const float* go = ws + paged_attention_ws_o_offset();
-        const float* gml = ws + paged_attention_ws_ml_offset(max_tokens, heads, d, S);
+        const AttnWs g = attn_ws(ws, max_tokens, heads, d, S);
+        const float *go = g.o, *gml = g.ml;
         const size_t lds = (size_t)heads * d * sizeof(f16);
         if (q)
             hipLaunchKernelGGL((heads_hadamard_merge_cols_kernel<32, true>), dim3(T), dim3(512), lds, st, go, gml, S, out_f16, q, scale,
@@ -824,8 +823,8 @@ int heads_hadamard_merge(const float* ws, int max_tokens, int n_splits, f16* out
         return 0;
     }
     if (!(heads == 32 || heads == 64) || n_splits < 1 || T > max_tokens) return -1;
-    const float* ws_o = ws + paged_attention_ws_o_offset();
-    const float* ws_ml = ws + paged_attention_ws_ml_offset(max_tokens, heads, d, n_splits);
+    const AttnWs w = attn_ws(ws, max_tokens, heads, d, n_splits);
+    const float *ws_o = w.o, *ws_ml = w.ml;
     const bool quant = q != nullptr;
     static const int spread = QS_DEV_KNOB("QSPEC_HHM_SPREAD", 1);   // (0: one workgroup per token also for the fp16 form)
     if (!quant && heads == 32 && spread && T * 8 <= 1024) {
@@ -854,8 +853,8 @@ int heads_hadamard_merge_spread(const float* ws, int max_tokens, int n_splits, f
                                 int T, int heads, int d, hipStream_t st) {
     if (T == 0) return 0;
     if (d != 128 || heads != 32 || n_splits < 1 || T > max_tokens || T * 8 > 1024) return -1;
-    const float* ws_o = ws + paged_attention_ws_o_offset();
-    const float* ws_ml = ws + paged_attention_ws_ml_offset(max_tokens, heads, d, n_splits);
+    const AttnWs w = attn_ws(ws, max_tokens, heads, d, n_splits);
+    const float *ws_o = w.o, *ws_ml = w.ml;
     hipLaunchKernelGGL(heads_hadamard_merge_spread32_kernel<true>, dim3(T, 8), dim3(512), 0, st, ws_o, ws_ml, n_splits, out_f16,
                        had_scale, part_amax);
     return 0;

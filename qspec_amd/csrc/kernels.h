@@ -156,7 +156,7 @@ int prefetch_l2(const void* p, size_t bytes, int workgroups, hipStream_t st);
 int prefetch_tiles(const void* p, size_t tile_bytes, int first_tile, int ntiles, int workgroups, hipStream_t st);
 #endif
 
-// attention.hip
+// rope_cache.hip
 int rope_kv_write(const int64_t* positions, f16* qkv, const f16* cos_sin_cache, void* key_cache, void* value_cache,
                   const int64_t* slot_mapping, int T, int nq, int nkv, int d, int rot_dim, hipStream_t st, KvQuant kq = KvQuant());
 int rotary_embedding(const int64_t* positions, f16* q, f16* k, const f16* cos_sin_cache, int T, int nq, int nkv,
@@ -164,14 +164,14 @@ int rotary_embedding(const int64_t* positions, f16* q, f16* k, const f16* cos_si
 int reshape_and_cache_flash(const f16* key, const f16* value, void* key_cache, void* value_cache,
                             const int64_t* slot_mapping, int T, int nkv, int d, int64_t k_stride, int64_t v_stride,
                             hipStream_t st, KvQuant kq = KvQuant());
+// attention.hip (host plan; kernels in attention_decode.hip, attention_prefill.hip, attention_generic.hip; the workspace layout
+// the consumers of the partials read: attention_common.cuh, attn_ws)
 int paged_attention(const f16* q, int64_t q_stride, const void* key_cache, const void* value_cache,
                     const int32_t* block_tables, int max_blocks, const int32_t* ctx_lens, const int32_t* q_start,
                     int n_seqs, int max_q_len, int nq, int nkv, int d, int block_size, float sm_scale, int n_splits,
                     float* ws, f16* out, hipStream_t st, KvQuant kq = KvQuant());
 size_t paged_attention_ws_bytes(int T, int nq, int d, int n_splits);
-size_t paged_attention_ws_o_offset();
 int paged_attention_generic_splits(int n_splits);   // head sizes other than 128: the splits actually used for a caller's n_splits
-size_t paged_attention_ws_ml_offset(int Tmax, int nq, int d, int n_splits);
 
 // sampler.hip
 int embedding(const int64_t* ids, const f16* table, f16* out, int T, int H, int V, hipStream_t st);

@@ -183,18 +183,7 @@ inline int stream_grid(int ntiles, int cap) {
     const int per = (ntiles + cap - 1) / cap;
     return (ntiles + per - 1) / per;
 }
-// Dynamic LDS beyond the 64 KiB a kernel gets unasked: opt in, once per kernel (one `static` per KERN) and again only when
-// a launch needs more than any before it.  first_use: the kernel's LDS size is fixed and always above 64 KiB -- set it
-// on the first launch without looking at the size.  0, or -8 when the runtime refuses.
-template <auto KERN>
-static int stream_lds_optin(size_t lds, bool first_use = false) {
-    static size_t attr_set = 0;
-    if (first_use ? attr_set != 0 : (lds <= 64 * 1024 || lds <= attr_set)) return 0;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return -8;
-    attr_set = lds;
-    return 0;
-}
+// (the opt-in to more than 64 KiB of dynamic LDS: common.cuh, lds_optin)
 
 // The argument block of an entry function: weights and shape, then the activations, then the QKV epilogue's operands.
 inline StreamArgs stream_args(const int8_t* wq, const f16* ws, int M, int N, int K) {

@@ -9,7 +9,7 @@ srcs=$(sed -n 's/^SRCS *= *//p' qspec_amd/csrc/Makefile)   # the library's one s
 [ -n "$srcs" ] || { echo "no SRCS in qspec_amd/csrc/Makefile" >&2; exit 1; }
 for s in $srcs; do
   f=${s%.hip}; src=qspec_amd/csrc/$s; obj=build_dev/$name/$f.o
-  if [ ! -f $obj ] || [ $src -nt $obj ] || [ qspec_amd/csrc/common.cuh -nt $obj ] || [ qspec_amd/csrc/stream_common.cuh -nt $obj ] || [ "$FORCE" = 1 ]; then
+  if [ ! -f $obj ] || [ $src -nt $obj ] || [ qspec_amd/csrc/common.cuh -nt $obj ] || [ qspec_amd/csrc/stream_common.cuh -nt $obj ] || [ qspec_amd/csrc/attention_common.cuh -nt $obj ] || [ "$FORCE" = 1 ]; then
     /opt/rocm/bin/hipcc $extra -DQS_EXPERIMENTAL -O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -fno-fast-math \
       -fhip-fp32-correctly-rounded-divide-sqrt -Wno-unused-function -Iqspec_amd/csrc -c $src -o $obj &
   fi

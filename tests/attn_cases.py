@@ -1,5 +1,5 @@
 """Paged-attention cases for the parity tests: a float64 reference, a case builder over block size, block-table width,
-context split count and score regime, and the dispatch rule of attention.hip: paged_attention() restated in Python so
+context split count and score regime, and the launch plan of attention.hip: attn_form() restated in Python so
 that a test can assert that the case list reaches every kernel instantiation.
 
 Every case poisons what no kernel may read.  Slots past a sequence's context in its last block and the blocks named by
@@ -26,7 +26,7 @@ import numpy as np
 POISON = 60000.0
 REGIMES = ("smooth", "peaked", "sink", "negative", "future_trap")
 SPLITS = (16, 8, 4, 3, 1)            # every value engine.n_splits_for returns for the BASELINE configs
-CHUNK, FA_ROWS, MAXR, MAXSPLIT = 128, 64, 16, 64   # attention.hip: QS_ATT_CHUNK, QS_FA_ROWS, QS_ATT_MAXR, QS_ATT_MAXSPLIT
+CHUNK, FA_ROWS, MAXR, MAXSPLIT = 128, 64, 16, 64   # attention_common.cuh: QS_ATT_CHUNK, QS_FA_ROWS, QS_ATT_MAXR, QS_ATT_MAXSPLIT
 
 
 @dataclass(frozen=True)
@@ -181,7 +181,7 @@ def merge_partials_f64(o, ml):
     return (w[..., None] * o).sum(axis=2) / (w * l).sum(axis=2)[..., None]
 
 
-# ------------------------------------------------------------------ dispatch rule of attention.hip: paged_attention()
+# ------------------------------------------------------------------ launch plan of attention.hip: attn_form()
 
 def generic_splits(n_splits):
     """attention.hip: paged_attention_generic_splits."""

@@ -1,6 +1,6 @@
 """CPU side of the paged-attention matrix (tests/attn_cases.py): the CPU oracle against the float64 reference on every
 case of the GPU matrix with contexts <= 2048, the reference (and the oracle) blind to the poisoned slots, the regimes
-doing what they claim, and the case list reaching every kernel instantiation of attention.hip: paged_attention()."""
+doing what they claim, and the case list reaching every kernel instantiation paged_attention() (attention.hip) launches."""
 import numpy as np
 import pytest
 
@@ -79,7 +79,7 @@ def test_regimes_have_the_claimed_scores():
 
 
 def test_matrix_covers_every_dispatch_row():
-    """attention.hip: paged_attention() at default knobs -- prefill kernel, paged_attention_kernel<PF, BT> with and
+    """attention.hip: attn_form() at default knobs -- prefill kernel, paged_attention_kernel<PF, BT> with and
     without out, paged_attention_waves_kernel<BT, 4, FAST>, the generic head-size kernels -- each reached by at least
     one case of the GPU matrix (a pruned case list or a changed rule fails here)."""
     reached = set().union(*(A.path_rows(c) for c in A.GPU_CASES))
@@ -102,22 +102,48 @@ def test_matrix_covers_every_dispatch_row():
     assert any(c.regime == "future_trap" and c.q_len > 1 and A.kernel_path(c).startswith("chunk") for c in cs)
 
 
+def _function_body(src, signature):
+    """The text between the braces of the function whose definition starts with `signature`."""
+    i = src.index(signature)
+    j = src.index("{", i + len(signature) - 1)
+    depth, k = 0, j
+    while True:
+        depth += {"{": 1, "}": -1}.get(src[k], 0)
+        if depth == 0:
+            return src[j + 1:k]
+        k += 1
+
+
 def test_dispatch_rule_matches_the_kernel_source():
-    """The Python rule restates attention.hip; the constants it copies and the conditions it mirrors are read back from
-    the source, so that a change there without a change here fails."""
+    """The Python rule restates attention.hip: attn_form(); the constants it copies (attention_common.cuh) and the conditions
+    it mirrors are read back from the source, so that a change there without a change here fails.  Every condition of the
+    launch plan lies inside attn_form() itself; the split clamp of the generic head sizes is the one-line function attn_form
+    calls (hadamard.hip calls it too)."""
     import os
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "qspec_amd", "csrc",
-                            "attention.hip")).read()
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "qspec_amd", "csrc")
+    consts = open(os.path.join(csrc, "attention_common.cuh")).read()
     for name, v in (("QS_ATT_CHUNK", A.CHUNK), ("QS_FA_ROWS", A.FA_ROWS), ("QS_ATT_MAXR", A.MAXR),
                     ("QS_ATT_MAXSPLIT", A.MAXSPLIT)):
-        assert f"#define {name} {v}" in src, name
-    for cond in ("n_splits == 1 && (max_q_len << group_log2) >= 2 * QS_FA_ROWS",
-                 "((int64_t)max_blocks << bs_log2) > (int64_t)QS_ATT_CHUNK * n_splits",
-                 "if (!out && (aw_env >= 0 ? aw_env != 0 : long_splits))",
-                 "if (max_blocks <= 128 && bs_log2 >= 4 && fast_env)",
-                 "(size_t)n_seqs * nkv * n_rb * n_splits <= 256",
-                 "const bool btreg = max_blocks <= 128;",
-                 "const bool partials = !out || S > 1;",
-                 "if (d % 8 == 0 && d >= 8)",
-                 "(n_splits > 4 ? 4 : n_splits)"):
-        assert cond in src, cond
+        assert f"#define {name} {v}" in consts, name
+    src = open(os.path.join(csrc, "attention.hip")).read()
+    form = _function_body(src, "static AttnForm attn_form(const AttnArgs& a) {")
+    for cond in ("const int rows = a.max_q_len << f.group_log2;",
+                 "if (fa_env && a.n_splits == 1 && rows >= 2 * QS_FA_ROWS)",
+                 "((int64_t)a.max_blocks << f.bs_log2) > (int64_t)QS_ATT_CHUNK * a.n_splits",
+                 "if (!a.out && (aw_env >= 0 ? aw_env != 0 : long_splits))",
+                 "f.fast = f.bt && f.bs_log2 >= 4 && fast_env;",
+                 "(size_t)a.n_seqs * a.nkv * f.n_rb * a.n_splits <= 256",
+                 "f.bt = a.max_blocks <= 128;",
+                 "const bool partials = !a.out || S > 1;",
+                 "if (a.d % 8 == 0 && a.d >= 8)",
+                 "const int S = paged_attention_generic_splits(a.n_splits);"):
+        assert cond in form, cond
+    assert "(n_splits > 4 ? 4 : n_splits)" in _function_body(src, "int paged_attention_generic_splits(int n_splits) {")
+    # the dev knobs of the family are read in attn_form and nowhere else
+    sources = [os.path.join(d, f) for d, _, fs in os.walk(csrc) for f in fs if f.endswith((".hip", ".cuh", ".h", ".inc"))]
+    assert any(os.path.dirname(p) != csrc for p in sources)   # the experimental includes are among them
+    for p in sources:
+        text = open(p).read()
+        text = text.replace(form, "") if p == os.path.join(csrc, "attention.hip") else text
+        assert 'QS_DEV_KNOB("QSPEC_ATTN_' not in text, p
+    assert form.count('QS_DEV_KNOB("QSPEC_ATTN_') == 5

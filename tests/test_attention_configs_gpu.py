@@ -13,7 +13,7 @@ from test_kernels_gpu import assert_close_1e3
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-CNT_SLOTS = 4096   # attention.hip: QS_ATT_CNT_SLOTS, ints ahead of the partials in the workspace
+CNT_SLOTS = 4096   # attention_common.cuh: QS_ATT_CNT_SLOTS, ints ahead of the partials in the workspace
 
 
 @pytest.fixture(scope="module")

@@ -883,7 +883,7 @@ def test_spread_head_hadamard_and_quantiser_in_the_o_proj_prologue(ops, oracle, 
 
 def _attn_partials_ws(ops, T, heads, d, S, o, m, l):
     """A paged_attention workspace holding the given per-split partials: [ticket counters | o [T, heads, S, d] | (m, l)
-    [T, heads, S, 2]] fp32 (attention.hip: paged_attention, out = NULL)."""
+    [T, heads, S, 2]] fp32 (attention_common.cuh: attn_ws; paged_attention, out = NULL)."""
     total = ops.paged_attention_workspace_bytes(T, heads, d, S) // 4
     cnt = total - T * heads * S * (d + 2)
     ws = torch.zeros(total, dtype=torch.float32, device=DEV)

@@ -19,7 +19,7 @@ from test_kernels_gpu import assert_close_1e3, rand_hidden, rand_w4
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-CNT_SLOTS = 4096   # attention.hip: QS_ATT_CNT_SLOTS
+CNT_SLOTS = 4096   # attention_common.cuh: QS_ATT_CNT_SLOTS
 SENTINEL = 0x5A
 SCALES = [(1.0, 1.0), (0.75, 1.5)]
 
