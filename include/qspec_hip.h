@@ -287,16 +287,24 @@ int qspec_rope_kv_write(const int64_t* positions, qspec_half* qkv, const qspec_h
  * out == NULL: the context splits are NOT merged; their partials (o, m, l) stay in the workspace for
  * qspec_heads_hadamard_merged, which merges them in front of the head transform (the launch boundary then is the
  * hand-off between the split workgroups and no ticket / fence is needed).
- * Three kernels sit behind this entry (attention.hip: attn_form), chosen from the shape alone: 16-row workgroups walking 128-key
- * chunks (decode / verify, splits of at most one chunk; also every out != NULL call with n_splits > 1); the same grid
- * with the keys over the waves of a workgroup (out == NULL and block_tables wide enough for splits longer than 128
- * keys); 64-row flash-style workgroups for prompt-sized queries (n_splits == 1, max_q_len * num_heads / num_kv_heads
- * >= 128).  Every block_tables entry must be a valid block number (unused tail entries: 0, as vLLM pads them): rows
+ * Four kernels sit behind this entry (attention.hip: attn_form), chosen from the shape alone.  With
+ * rows = max_q_len * num_heads / num_kv_heads: rows >= 128 and n_splits == 1: 64-row flash-style workgroups for prompt-sized
+ * queries; rows >= 128 and n_splits > 1: the same workgroups over n_splits context splits of whole 64-key chunks (a prompt
+ * suffix behind a cached context: prefix hits, chunked prefill), split z of a sequence owning the keys [z L, (z + 1) L),
+ * L = ceil(ctx / n_splits) rounded up to 64; out != NULL merges the partials with a second small launch (no ticket counters).
+ * rows < 128: 16-row workgroups walking 128-key chunks (decode / verify, splits of at most one chunk; also every
+ * out != NULL call with n_splits > 1); the same grid with the keys over the waves of a workgroup (out == NULL and
+ * block_tables wide enough for splits longer than 128 keys).  Every block_tables entry must be a valid block number (unused tail entries: 0, as vLLM pads them): rows
  * past a sequence's context are read (clamped prefetch) and masked, never used.  head_size != 128 (even, <= 256; TinyLlama:
  * 64): a generic kernel without matrix cores, one workgroup per (token, head, split) over min(n_splits, 4) context splits of
  * whole 16-key groups; out != NULL merges them with a second small launch, out == NULL (head_size % 8 == 0) leaves the
  * partials to qspec_heads_hadamard_merged -- the same merge expression, so the same bits either way. */
 size_t qspec_paged_attention_workspace_bytes(int max_tokens, int num_heads, int head_size, int n_splits);
+/* The kernel family of the launch plan qspec_paged_attention makes for a call of this shape (merged: out != NULL), computed
+ * by the plan itself without a device: 0 refused or nothing to launch, 1 generic scalar, 2 generic vector, 3 prompt-sized
+ * (64 rows), 4 keys over waves, 5 128-key chunks, 6 prompt-sized with context splits. */
+int qspec_paged_attention_family(int n_seqs, int max_q_len, int num_heads, int num_kv_heads, int head_size, int block_size,
+                                 int max_blocks_per_seq, int n_splits, int merged);
 int qspec_paged_attention(const qspec_half* q, int64_t q_stride, const qspec_half* key_cache,
                           const qspec_half* value_cache, const int32_t* block_tables, int max_blocks_per_seq,
                           const int32_t* ctx_lens, const int32_t* q_start, int n_seqs, int tokens, int max_q_len,

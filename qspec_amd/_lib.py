@@ -80,6 +80,7 @@ SIGNATURES = {
     "qspec_rope_kv_write": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "qspec_heads_hadamard_merged": (_i, [_vp, _i, _i, _vp, _vp, _vp, _f, _f, _i, _i, _i, _vp]),
     "qspec_paged_attention_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "qspec_paged_attention_family": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "qspec_paged_attention": (_i, [_vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp,
                                    _vp, _vp]),
     "qspec_reshape_and_cache_flash_kv8": (_i, [_vp, _vp, _vp, _vp, _f, _f, _vp, _i, _i, _i, _i64, _i64, _vp]),

@@ -65,6 +65,16 @@ static AttnForm attn_form(const AttnArgs& a) {
         f.lds = (size_t)QS_FA_KEYS * 256 + (size_t)QS_FA_KEYS * QS_ATT_VSTRIDE * 2 + (size_t)4 * 2 * 16 * 72 * 2;
         return f;
     }
+    // a prompt-sized suffix behind a cached context (prefix hit, chunked prefill): the same 64-row workgroups over grid.z
+    // context splits of whole 64-key chunks; partials in the chunk kernel's layout, merged by a second launch (out != NULL) or by
+    // the head transform.  No ticket counters: the -4 refusal below does not apply.
+    if (fa_env && a.n_splits > 1 && rows >= 2 * QS_FA_ROWS) {
+        f.family = ATTN_PREFILL_SPLIT; f.partials = true; f.merge = a.out != nullptr;
+        f.n_rb = (rows + QS_FA_ROWS - 1) / QS_FA_ROWS;
+        f.grid = dim3(a.n_seqs, a.nkv * f.n_rb, a.n_splits);
+        f.lds = (size_t)QS_FA_KEYS * 256 + (size_t)QS_FA_KEYS * QS_ATT_VSTRIDE * 2 + (size_t)4 * 2 * 16 * 72 * 2;
+        return f;
+    }
     f.n_rb = (rows + QS_ATT_MAXR - 1) / QS_ATT_MAXR;
     if (a.out && (size_t)a.n_seqs * a.nkv * f.n_rb > QS_ATT_CNT_SLOTS) return attn_no_launch(-4);   // ticket counters: in-kernel merge only
     f.partials = true; f.merge = a.out != nullptr;
@@ -107,11 +117,24 @@ int paged_attention(const f16* q, int64_t q_stride, const void* key_cache, const
     const AttnForm f = attn_form(a);
     switch (f.family) {
         case ATTN_NO_LAUNCH: return f.rc;
-        case ATTN_PREFILL: return attn_launch_prefill(a, f);
+        case ATTN_PREFILL: case ATTN_PREFILL_SPLIT: return attn_launch_prefill(a, f);
         case ATTN_WAVES: return attn_launch_waves(a, f);
         case ATTN_CHUNK: return attn_launch_chunk(a, f);
         default: return attn_launch_generic(a, f);
     }
+}
+
+// The family of the plan a call with these arguments gets (0: refused or nothing to launch): attn_form() itself, which makes
+// no HIP call, so this works without a device.
+int paged_attention_family(int n_seqs, int max_q_len, int nq, int nkv, int d, int block_size, int max_blocks, int n_splits,
+                           bool merged) {
+    if (nq <= 0 || nkv <= 0) return ATTN_NO_LAUNCH;
+    static float ws_tag;   // attn_form() only asks whether ws / out are given
+    static f16 out_tag;
+    AttnArgs a{};
+    a.max_blocks = max_blocks; a.n_seqs = n_seqs; a.max_q_len = max_q_len; a.nq = nq; a.nkv = nkv; a.d = d;
+    a.block_size = block_size; a.n_splits = n_splits; a.ws = &ws_tag; a.out = merged ? &out_tag : nullptr;
+    return attn_form(a).family;
 }
 
 }  // namespace qspec

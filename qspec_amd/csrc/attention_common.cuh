@@ -155,7 +155,7 @@ struct AttnArgs {
     hipStream_t st;
 };
 // The launch plan attn_form() (attention.hip) decides from the arguments alone.
-enum AttnFamily { ATTN_NO_LAUNCH, ATTN_GENERIC, ATTN_GENERIC_VEC, ATTN_PREFILL, ATTN_WAVES, ATTN_CHUNK };
+enum AttnFamily { ATTN_NO_LAUNCH, ATTN_GENERIC, ATTN_GENERIC_VEC, ATTN_PREFILL, ATTN_WAVES, ATTN_CHUNK, ATTN_PREFILL_SPLIT };
 struct AttnForm {
     AttnFamily family;
     int rc;                   // ATTN_NO_LAUNCH: what paged_attention() returns (0: nothing to do, < 0: the refusal)
@@ -163,13 +163,13 @@ struct AttnForm {
     int nw;                   // waves per workgroup of the waves kernel
     int S;                    // context splits of the launch (generic head sizes: paged_attention_generic_splits)
     bool partials, merge;     // (o, m, l) of every split go to the workspace / the splits are merged into `out`: inside the
-                              // chunk kernel, by a second launch for the generic head sizes
+                              // chunk kernel, by a second launch for the generic head sizes and the context-split prompt kernel
     int bs_log2, group_log2, n_rb;   // n_rb: row blocks per kv head
     dim3 grid; size_t lds;
 };
 int attn_launch_chunk(const AttnArgs& a, const AttnForm& f);     // attention_decode.hip
 int attn_launch_waves(const AttnArgs& a, const AttnForm& f);
-int attn_launch_prefill(const AttnArgs& a, const AttnForm& f);   // attention_prefill.hip
+int attn_launch_prefill(const AttnArgs& a, const AttnForm& f);   // attention_prefill.hip (ATTN_PREFILL, ATTN_PREFILL_SPLIT)
 int attn_launch_generic(const AttnArgs& a, const AttnForm& f);   // attention_generic.hip
 
 // Workspace: [QS_ATT_CNT_SLOTS ticket counters (int) | o partials [Tmax, nq, S, d] | (m, l) partials [Tmax, nq, S, 2]], sized by
@@ -180,6 +180,7 @@ inline AttnWs attn_ws(const float* ws, size_t Tmax, int nq, int d, int S) {
     float* o = const_cast<float*>(ws) + QS_ATT_CNT_SLOTS;
     return AttnWs{reinterpret_cast<int*>(const_cast<float*>(ws)), o, o + Tmax * nq * S * d};
 }
+void attn_launch_split_merge(const AttnArgs& a, const AttnForm& f, const AttnWs& w);   // attention_generic.hip: partials -> a.out
 // One launch of the plan: the eight arguments every attention kernel starts with, then its own.  LDS beyond 64 KiB is
 // opted in to where the plan asks for it.
 template <auto KERN, typename KVT, typename... Own>

@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void paged_attention_generic_vec_kernel(
     }
 }
 
-// Split merge for the generic head sizes when the caller wants fp16 rows (the reference-order path; the engine merges in
+// Split merge for the generic head sizes and for the context-split prompt kernel (attention_prefill.hip) when the caller wants fp16 rows (the reference-order path; the engine merges in
 // the head-transform launch, hadamard.hip: heads_hadamard_merge_cols_kernel -- same expression, same bits):
 // out = h( sum_s w_s o_s / sum_s w_s l_s ), w_s = e^(m_s - M), splits in order.
 __global__ __launch_bounds__(256) void paged_attention_generic_merge_kernel(const float* __restrict__ ws_o,
@@ -242,6 +242,12 @@ __global__ __launch_bounds__(256) void paged_attention_generic_merge_kernel(cons
     }
 }
 
+void attn_launch_split_merge(const AttnArgs& a, const AttnForm& f, const AttnWs& w) {
+    const size_t Tm = (size_t)a.n_seqs * a.max_q_len;
+    hipLaunchKernelGGL(paged_attention_generic_merge_kernel, dim3((unsigned)(Tm * a.nq)), dim3(256), 0, a.st, w.o, w.ml, f.S, a.d,
+                       a.out, a.q_start, a.n_seqs, a.nq);
+}
+
 template <typename KVT>
 static int launch_generic_vec(const AttnArgs& a, const AttnForm& f) {
     const size_t Tm = (size_t)a.n_seqs * a.max_q_len;
@@ -249,9 +255,7 @@ static int launch_generic_vec(const AttnArgs& a, const AttnForm& f) {
     if (const int rc = attn_launch<paged_attention_generic_vec_kernel<KVT>, KVT>(256, a, f, a.n_seqs, a.nq, a.nkv, a.d, a.block_size,
                                                                                  a.sm_scale, a.out, w.o, w.ml, a.v_scale))
         return rc;
-    if (f.merge)
-        hipLaunchKernelGGL(paged_attention_generic_merge_kernel, dim3((unsigned)(Tm * a.nq)), dim3(256), 0, a.st, w.o, w.ml, f.S,
-                           a.d, a.out, a.q_start, a.n_seqs, a.nq);
+    if (f.merge) attn_launch_split_merge(a, f, w);
     return 0;
 }
 int attn_launch_generic(const AttnArgs& a, const AttnForm& f) {

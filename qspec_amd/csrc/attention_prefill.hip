@@ -16,9 +16,18 @@ namespace qspec {
 //   * a wave's S = Q K^T (16 x 64), its running (max, sum) and its 16 x 128 output live in registers; only P goes
 //     through a wave-private LDS tile to change from the accumulator layout to the A-operand layout (as hi + lo fp16,
 //     two MFMAs, so that P.V keeps fp32-class accuracy);
-//   * no context split: one (o, m, l) per row, stored as the single-split partial heads_hadamard_merge expects and/or
-//     normalised into `out`.
-template <typename KVT>   // see paged_attention_kernel
+//   * SPLIT = false: no context split: one (o, m, l) per row, stored as the single-split partial heads_hadamard_merge
+//     expects and/or normalised into `out`.
+//   * SPLIT = true (a short suffix behind a long cached context: too few row blocks to fill the chip): grid.z context splits.
+//     Split z of a sequence owns the keys [z L, min((z + 1) L, ctx)), L = ceil(ctx / S) rounded up to a whole 64-key chunk, from
+//     ctx alone; its walk is the same chunk walk offset by z L and clipped by the workgroup's causal horizon.  It stores the
+//     partial (o, m, l) of (token, head, split) in the layout of the chunk kernel and never writes `out`: the merge is a
+//     launch of its own (attn_launch_split_merge) or the head transform's.  A row whose position lies in front of the split
+//     sees no key at all: its running maximum stays -inf through every chunk.  online_softmax_tiles takes exactly that
+//     case (m_new = -inf: p = 0; m_old = -inf: alpha = 0, never e^(-inf + inf)), so such a row ends with the neutral partial
+//     (0, -inf, 0) an empty split of the chunk kernel stores; a workgroup whose whole range lies behind its horizon walks
+//     no chunk and stores the same.
+template <typename KVT, bool SPLIT>   // KVT: see paged_attention_kernel
 __global__ __launch_bounds__(256) void paged_attention_prefill_kernel(
     const f16* __restrict__ q, int64_t q_stride, const KVT* __restrict__ key_cache, const KVT* __restrict__ value_cache,
     const int32_t* __restrict__ block_tables, int max_blocks, const int32_t* __restrict__ ctx_lens,
@@ -47,7 +56,16 @@ __global__ __launch_bounds__(256) void paged_attention_prefill_kernel(
     // causal horizon of the workgroup: the last valid row's token sees keys 0 .. pos
     const int last_row = min(rb * QS_FA_ROWS + QS_FA_ROWS - 1, total_rows - 1);
     const int n_keys = min(ctx, ctx - qlen + (last_row >> group_log2) + 1);
-    const int n_chunks = (n_keys + QS_FA_KEYS - 1) / QS_FA_KEYS;
+    // keys [k0, k1) of this workgroup: all visible ones, or the split's share of them
+    int k0 = 0, k1 = n_keys;
+    int n_chunks = (n_keys + QS_FA_KEYS - 1) / QS_FA_KEYS;
+    if constexpr (SPLIT) {
+        const int S = gridDim.z;
+        const int L = (((ctx + S - 1) / S) + QS_FA_KEYS - 1) & ~(QS_FA_KEYS - 1);
+        k0 = blockIdx.z * L;
+        k1 = min(k0 + L, n_keys);
+        n_chunks = max(k1 - k0 + QS_FA_KEYS - 1, 0) / QS_FA_KEYS;   // 0: the range lies behind the horizon
+    }
 
     // Q fragments: lane (row c16, d slice 8 g4 + 32 j); rows past the end repeat the last valid row (never stored)
     u32x4 qfrag[4];
@@ -83,10 +101,10 @@ __global__ __launch_bounds__(256) void paged_attention_prefill_kernel(
             vreg[i] = kv_load8<KVT>(vp + 8 * i);
         }
     };
-    stage_load(0);
+    stage_load(k0);
     for (int c = 0; c < n_chunks; c++) {
-        const int kb = c * QS_FA_KEYS;
-        const int nk = min(n_keys - kb, QS_FA_KEYS);
+        const int kb = k0 + c * QS_FA_KEYS;
+        const int nk = min(k1 - kb, QS_FA_KEYS);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int ci = spart * 4 + i;
@@ -153,7 +171,8 @@ __global__ __launch_bounds__(256) void paged_attention_prefill_kernel(
     for (int reg = 0; reg < 4; reg++) {
         const int rr = rbase + 4 * g4 + reg;
         if (rr < total_rows) {
-            const size_t th = token_head(rr, qs, group_log2, kvh, gmask, nq);
+            size_t th = token_head(rr, qs, group_log2, kvh, gmask, nq);
+            if constexpr (SPLIT) th = th * gridDim.z + blockIdx.z;   // [T, nq, S, ..]
             if (ws_o) {
 #pragma unroll
                 for (int dt = 0; dt < 8; dt++) ws_o[th * D + dt * 16 + c16] = o[dt][reg];
@@ -162,7 +181,7 @@ __global__ __launch_bounds__(256) void paged_attention_prefill_kernel(
                     ws_ml[th * 2 + 1] = row_l[reg];
                 }
             }
-            if (out) {
+            if (!SPLIT && out) {
 #pragma unroll
                 for (int dt = 0; dt < 8; dt++) out[th * D + dt * 16 + c16] = f2h(o[dt][reg] / row_l[reg]);
             }
@@ -170,14 +189,18 @@ __global__ __launch_bounds__(256) void paged_attention_prefill_kernel(
     }
 }
 
-template <typename KVT>
+template <typename KVT, bool SPLIT>
 static int launch_prefill(const AttnArgs& a, const AttnForm& f) {
     const AttnWs w = attn_ws(a.ws, (size_t)a.n_seqs * a.max_q_len, a.nq, a.d, f.S);
-    return attn_launch<paged_attention_prefill_kernel<KVT>, KVT>(256, a, f, a.nq, a.nkv, f.bs_log2, f.group_log2, a.sm_scale,
-                                                                 f.n_rb, w.o, w.ml, a.out, a.v_scale);
+    if (const int rc = attn_launch<paged_attention_prefill_kernel<KVT, SPLIT>, KVT>(256, a, f, a.nq, a.nkv, f.bs_log2, f.group_log2,
+                                                                                    a.sm_scale, f.n_rb, w.o, w.ml, a.out, a.v_scale))
+        return rc;
+    if (f.merge) attn_launch_split_merge(a, f, w);   // SPLIT, out != NULL: no ticket counters, the launch boundary is the hand-off
+    return 0;
 }
 int attn_launch_prefill(const AttnArgs& a, const AttnForm& f) {
-    return a.fp8 ? launch_prefill<uint8_t>(a, f) : launch_prefill<f16>(a, f);
+    if (f.family == ATTN_PREFILL_SPLIT) return a.fp8 ? launch_prefill<uint8_t, true>(a, f) : launch_prefill<f16, true>(a, f);
+    return a.fp8 ? launch_prefill<uint8_t, false>(a, f) : launch_prefill<f16, false>(a, f);
 }
 
 }  // namespace qspec

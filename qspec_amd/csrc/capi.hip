@@ -647,6 +647,11 @@ int qspec_rope_kv_write(const int64_t* positions, qspec_half* qkv, const qspec_h
 size_t qspec_paged_attention_workspace_bytes(int max_tokens, int num_heads, int head_size, int n_splits) {
     return qspec::paged_attention_ws_bytes(max_tokens, num_heads, head_size, n_splits);
 }
+int qspec_paged_attention_family(int n_seqs, int max_q_len, int num_heads, int num_kv_heads, int head_size, int block_size,
+                                 int max_blocks_per_seq, int n_splits, int merged) {
+    return qspec::paged_attention_family(n_seqs, max_q_len, num_heads, num_kv_heads, head_size, block_size, max_blocks_per_seq,
+                                         n_splits, merged != 0);
+}
 int qspec_paged_attention(const qspec_half* q, int64_t q_stride, const qspec_half* key_cache, const qspec_half* value_cache,
                           const int32_t* block_tables, int max_blocks_per_seq, const int32_t* ctx_lens, const int32_t* q_start,
                           int n_seqs, int tokens, int max_q_len, int num_heads, int num_kv_heads, int head_size, int block_size,

@@ -171,6 +171,8 @@ int paged_attention(const f16* q, int64_t q_stride, const void* key_cache, const
                     int n_seqs, int max_q_len, int nq, int nkv, int d, int block_size, float sm_scale, int n_splits,
                     float* ws, f16* out, hipStream_t st, KvQuant kq = KvQuant());
 size_t paged_attention_ws_bytes(int T, int nq, int d, int n_splits);
+int paged_attention_family(int n_seqs, int max_q_len, int nq, int nkv, int d, int block_size, int max_blocks, int n_splits,
+                           bool merged);   // the AttnFamily (attention_common.cuh) of the call's launch plan; no HIP call
 int paged_attention_generic_splits(int n_splits);   // head sizes other than 128: the splits actually used for a caller's n_splits
 
 // sampler.hip

@@ -644,6 +644,18 @@ def paged_attention_workspace_bytes(max_tokens, num_heads, head_size, n_splits) 
     return int(_lib.load().qspec_paged_attention_workspace_bytes(max_tokens, num_heads, head_size, n_splits))
 
 
+# attention_common.cuh: AttnFamily, as paged_attention_family returns it
+ATTN_NO_LAUNCH, ATTN_GENERIC, ATTN_GENERIC_VEC, ATTN_PREFILL, ATTN_WAVES, ATTN_CHUNK, ATTN_PREFILL_SPLIT = range(7)
+
+
+def paged_attention_family(n_seqs, max_q_len, num_heads, num_kv_heads, head_size, block_size, max_blocks_per_seq, n_splits,
+                           merged: bool) -> int:
+    """The kernel family paged_attention() launches for a call of this shape (0: refused, or nothing to launch); merged: `out`
+    given.  The library's own launch plan, evaluated without a device."""
+    return int(_lib.load().qspec_paged_attention_family(n_seqs, max_q_len, num_heads, num_kv_heads, head_size, block_size,
+                                                        max_blocks_per_seq, n_splits, int(bool(merged))))
+
+
 def paged_attention(q, q_stride, key_cache, value_cache, block_tables, ctx_lens, q_start, tokens, max_q_len,
                     num_heads, sm_scale, n_splits, workspace, out, k_scale: float = 1.0, v_scale: float = 1.0):
     """flash_attn_with_kvcache / flash_attn_varlen_func over the paged cache (flash_attn.py:741-830); an fp8 cache

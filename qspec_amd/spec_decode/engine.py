@@ -60,6 +60,24 @@ def n_splits_for(ctx: int, n_groups: int = 0) -> int:
     return 1
 
 
+PREFILL_SPLIT_ROWS = 64        # rows of a workgroup of the prompt attention kernels (QS_FA_ROWS)
+# Kmin, the shortest context split worth a workgroup of its own: measured (profiles/prefix_attention.txt)
+PREFILL_SPLIT_MIN_KEYS = 512
+
+
+def prefill_splits(q_lens: Sequence[int], ctx_lens: Sequence[int], num_kv_heads: int, group: int) -> int:
+    """Context splits of the attention of a PROMPT pass (q_lens[i] query tokens at the end of ctx_lens[i] keys; group = query
+    heads per kv head).  No sequence with keys in front of its queries -- every pass before prefix hits and chunked prefill
+    existed --: 1, the unsplit prompt kernel.  Otherwise the row blocks W = sum ceil(q group / 64) x kv heads that the unsplit
+    kernel would launch are multiplied until they fill the 256 CUs, S = 256 // W in 1 .. 16, but no split shorter than
+    PREFILL_SPLIT_MIN_KEYS keys: S <= ceil(longest context / Kmin)."""
+    if all(int(c) == int(q) for q, c in zip(q_lens, ctx_lens)):
+        return 1
+    W = sum(-(-int(q) * group // PREFILL_SPLIT_ROWS) for q in q_lens) * num_kv_heads
+    S = max(1, min(16, 256 // max(W, 1)))
+    return max(1, min(S, -(-max(int(c) for c in ctx_lens) // PREFILL_SPLIT_MIN_KEYS)))
+
+
 class QSpecEngine:
     def __init__(self, model: QuarotLlamaForCausalLM, num_speculative_tokens: int = 3, max_batch: int = 4,
                  max_model_len: int = 1024, block_size: int = 16, max_new_tokens: int = 1024, use_graph: bool = True,
@@ -200,6 +218,10 @@ class QSpecEngine:
     PREFILL_TOKEN_BUDGET = 4096   # tokens per prompt-pass forward when several requests are admitted together
     PROMPT_LOGPROB_ROWS = 256     # prompt rows per lm_head launch of the prompt logprobs (ONE fp16 [rows, V] buffer, made at first use)
     # logprobs (token_logprobs / take_prompt_logprobs): everything below stays None until a request asks for them
+    # chunked prefill (add_sequence: num_computed_tokens / token_chunk_size): both stay None until a prompt arrives in chunks
+    _prefilling: Optional[dict] = None        # slot -> its request while the prompt is only partly computed (_normalise_admission)
+    _reserved: Optional[dict] = None          # sample slot -> the prefilling slot that holds it for its additional samples
+    _prefix_scratch = None                    # (splits, Scratch) of the single-request prompt passes with context splits
     _first_probs: Optional[dict] = None       # slot -> (the processed distribution its first token was sampled from, row)
     _prompt_results: Optional[dict] = None    # slot -> host tensors waiting for take_prompt_logprobs()
     _plp_logits: Optional[torch.Tensor] = None
@@ -225,91 +247,80 @@ class QSpecEngine:
                          block_tables: Optional[Sequence[Optional[Sequence[int]]]] = None,
                          num_prompt_tokens: Optional[Sequence[Optional[int]]] = None,
                          prompt_logprobs: Optional[Sequence[Optional[int]]] = None,
-                         sample_slots: Optional[Sequence[Optional[Sequence[int]]]] = None) -> None:
+                         sample_slots: Optional[Sequence[Optional[Sequence[int]]]] = None,
+                         num_computed_tokens: Optional[Sequence[Optional[int]]] = None,
+                         token_chunk_sizes: Optional[Sequence[Optional[int]]] = None) -> None:
         """Admit several requests at once: one W4A16 forward over the concatenated prompts (flash-attn varlen form).
         num_prompt_tokens[i] (None: all of it): how many tokens of prompts[i] are the request's PROMPT -- a preempted
         request comes back with prompt + outputs as one token list, and the penalties / min_tokens tell the two apart.
         prompt_logprobs[i] (None: not asked for): SamplingParams.prompt_logprobs of request i -- the logprob and rank of every
         token of prompts[i] but the first plus that many best, from the RAW target logits; take_prompt_logprobs(slot) hands
         them over.  sample_slots[i] (None: none): further EMPTY slots that receive additional first-token samples of prompts[i]
-        (SamplingParams.n / best_of > 1) -- see add_sequence."""
-        cfg, dev = self.cfg, self.device
+        (SamplingParams.n / best_of > 1) -- see add_sequence.  num_computed_tokens[i] (None: 0) / token_chunk_sizes[i] (None:
+        the rest of the prompt): a prefix hit and / or one chunk of a chunked prefill -- see add_sequence; requests with
+        different (computed, chunk) share the forward."""
         n = len(slots)
         if n == 0:
             return
+        if len(set(slots)) != len(slots):
+            raise ValueError("a slot appears twice in one admission")
+        opt = lambda v: [None] * n if v is None else list(v)   # noqa: E731
+        tables, npts, plps = opt(block_tables), opt(num_prompt_tokens), opt(prompt_logprobs)
+        cs, qs = opt(num_computed_tokens), opt(token_chunk_sizes)
         extra = [()] * n if sample_slots is None else [tuple(int(c) for c in (e or ())) for e in sample_slots]
-        self._check_sample_slots(list(slots) + [c for e in extra for c in e])
         # Validate EVERY slot, prompt and block table before the first forward: a later request that does not fit must
         # not leave earlier ones of the same call admitted (their slots would be occupied here and free in the worker).
-        for i, b in enumerate(slots):
-            if not 0 <= b < self.B or self._len_ub[b] != 0:
-                raise ValueError(f"slot {b} is not an empty slot of this engine")
-            table = None if block_tables is None else block_tables[i]
-            if table is not None:
-                self._validate_block_table(table)
-            cap = self._capacity[b] if table is None else len(table) * self.block_size
-            T = len(prompts[i])
-            if T < 1 or T + 1 > min(cap, self.max_model_len):
-                raise ValueError(f"prompt of {T} tokens does not fit slot {b} (capacity {cap} tokens, max_model_len "
-                                 f"{self.max_model_len})" + ("" if cap else ": the request brought no block table"))
-        npts = [None] * n if num_prompt_tokens is None else list(num_prompt_tokens)
-        for i in range(n):
-            if npts[i] is not None and not 1 <= npts[i] <= len(prompts[i]):
-                raise ValueError(f"num_prompt_tokens {npts[i]} outside 1..{len(prompts[i])}")
-        plps = [None] * n if prompt_logprobs is None else list(prompt_logprobs)
-        for v in plps:
-            self._check_num_top(v)
+        reqs = [self._normalise_admission(slots[i], prompts[i], tables[i], npts[i], plps[i], extra[i], cs[i], qs[i])
+                for i in range(n)]
+        self._check_sample_slots([c for r in reqs for c in r.fresh_slots])
         if n == 1:
-            self.add_sequence(slots[0], prompts[0], None if block_tables is None else block_tables[0],
-                              num_prompt_tokens=npts[0], prompt_logprobs=plps[0], **({"sample_slots": extra[0]} if extra[0] else {}))
+            self._prompt_pass_one(reqs[0])
+            self._sync()
             return
-        if sum(len(p) for p in prompts) > self.PREFILL_TOKEN_BUDGET:
+        if sum(r.rows for r in reqs) > self.PREFILL_TOKEN_BUDGET:
             # several passes of at most PREFILL_TOKEN_BUDGET tokens (measured: 4 x 512 tokens in one pass 37 ms vs 49 ms
             # one by one, but 32 x 512 in one pass 335 ms vs 283 ms)
             group, tokens = [], 0
             for i in range(n + 1):
-                if i == n or (group and tokens + len(prompts[i]) > self.PREFILL_TOKEN_BUDGET):
-                    self.add_sequences_to([slots[j] for j in group], [prompts[j] for j in group],
-                                          None if block_tables is None else [block_tables[j] for j in group],
-                                          [npts[j] for j in group], [plps[j] for j in group], [extra[j] for j in group])
+                if i == n or (group and tokens + reqs[i].rows > self.PREFILL_TOKEN_BUDGET):
+                    if len(group) == 1:
+                        self._prompt_pass_one(group[0])
+                    else:
+                        self._prompt_pass_many(group)
                     group, tokens = [], 0
                 if i < n:
-                    group.append(i)
-                    tokens += len(prompts[i])
-            return
-        for i, b in enumerate(slots):
-            if block_tables is not None and block_tables[i] is not None:
-                self.set_block_table(b, block_tables[i])
-        lens = [len(p) for p in prompts]
+                    group.append(reqs[i])
+                    tokens += reqs[i].rows
+        else:
+            self._prompt_pass_many(reqs)
+        self._sync()
+
+    def _prompt_pass_many(self, reqs) -> None:
+        """One varlen forward over the rows of several requests (each: positions first .. c + q - 1 behind c valid keys)."""
+        cfg, dev = self.cfg, self.device
+        n = len(reqs)
+        for r in reqs:
+            if r.table is not None:
+                self.set_block_table(r.slot, r.table)
+        lens = [r.rows for r in reqs]
         Ttot, Tmax = sum(lens), max(lens)
-        s = Scratch(cfg, Ttot, n, Tmax, 1, dev, logits_rows=n)
-        ids = torch.tensor([t for p in prompts for t in p], dtype=torch.int64, device=dev)
-        pos = torch.cat([torch.arange(T, dtype=torch.int64, device=dev) for T in lens])
-        slot_map = torch.cat([self._slots_for(b, torch.arange(T, dtype=torch.int64, device=dev)) for b, T in zip(slots, lens)])
+        ctx = [r.c + r.q for r in reqs]
+        S = prefill_splits(lens, ctx, cfg.num_key_value_heads, cfg.num_attention_heads // cfg.num_key_value_heads)
+        s = Scratch(cfg, Ttot, n, Tmax, S, dev, logits_rows=n)
+        ids = torch.tensor([t for r in reqs for t in r.tokens[r.first:r.c + r.q]], dtype=torch.int64, device=dev)
+        pos = torch.cat([torch.arange(r.first, r.c + r.q, dtype=torch.int64, device=dev) for r in reqs])
+        slot_map = torch.cat([self._write_slots(r, torch.arange(r.first, r.c + r.q, dtype=torch.int64, device=dev)) for r in reqs])
         q_start = torch.tensor([0] + list(torch.tensor(lens).cumsum(0).tolist()), dtype=torch.int32, device=dev)
-        md = AttentionMetadata(slot_map, self.block_tables[list(slots)].contiguous(),
-                               torch.tensor(lens, dtype=torch.int32, device=dev), q_start, Tmax, 1)
+        md = AttentionMetadata(slot_map, self.block_tables[[r.slot for r in reqs]].contiguous(),
+                               torch.tensor(ctx, dtype=torch.int32, device=dev), q_start, Tmax, S)
         hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False, **self._kv_fw)
-        last = (q_start[1:].long() - 1)
-        rows, row_slots, row_lens = [], [], []      # one first-token row per request and per additional sample of it
-        for i, b in enumerate(slots):
-            self.sampling.admit_tokens(b, prompts[i], npts[i])
-            self._admit_samples(b, extra[i], prompts[i], npts[i])
-            rows += [i] * (1 + len(extra[i]))
-            row_slots += [b, *extra[i]]
-            row_lens += [lens[i]] * (1 + len(extra[i]))
-        first_hs = hs[last] if len(rows) == n else hs[last][torch.tensor(rows, dtype=torch.int64, device=dev)]
-        self._first_token(first_hs.contiguous(), s, row_slots, row_lens)
-        starts = q_start.tolist() if any(v is not None for v in plps) else None
-        for i, b in enumerate(slots):
-            if plps[i] is not None:
-                self._prompt_logprobs(b, hs[starts[i]:starts[i] + lens[i] - 1], prompts[i], plps[i])
-        torch.cuda.synchronize()
+        self._finish_prompt_pass(reqs, hs, q_start.tolist(), s)
 
     @torch.no_grad()
     def add_sequence(self, slot: int, prompt: Sequence[int], block_table: Optional[Sequence[int]] = None,
                      sync: bool = True, num_prompt_tokens: Optional[int] = None, prompt_logprobs: Optional[int] = None,
-                     sample_slots: Sequence[int] = ()) -> None:
+                     sample_slots: Sequence[int] = (), num_computed_tokens: int = 0,
+                     token_chunk_size: Optional[int] = None) -> None:
         """Admit a request into an empty slot: scorer-only W4A16 prompt pass (the proposer never runs on prefill,
         spec_decode_worker.py:699); the first generated token is the target's greedy token.  prompt_logprobs: see
         add_sequences_to.
@@ -318,48 +329,168 @@ class QSpecEngine:
         sample.  Every sample slot gets the parent's block table (the prompt's blocks are shared until the scheduler hands a
         sample its own copy: copy_blocks + set_block_table), the prompt in its token table, the parent's sampling parameters and
         its own first token; sample i (the parent is 0) of a seeded request draws with seed (seed + i * SAMPLE_SEED_STRIDE)
-        mod 2^64, unseeded samples with the engine stream (row-indexed: the rows differ)."""
-        cfg, dev, b = self.cfg, self.device, slot
+        mod 2^64, unseeded samples with the engine stream (row-indexed: the rows differ).
+
+        Prefix hits and chunked prefill (model_runner.py:482-590): `prompt` is always the request's FULL token list;
+        num_computed_tokens = c tokens of it already have valid K/V in the slot's block table (blocks another request filled, or
+        earlier chunks of this one), token_chunk_size = q tokens are computed now (None: the rest).  The pass computes rows
+        c .. c + q - 1 at positions c .. behind c keys read from the cache.  c >= len(prompt) (everything hit): the last token
+        alone is computed, c = len - 1.  c + q < len: the slot is PREFILLING afterwards -- occupied on the host (no admission,
+        fork or step may name it), still the empty slot seq_lens == 0 on the device, so every captured cycle runs on untouched;
+        the next call for it brings the same token list and c >= the count reached (larger: the caller vouches for the tokens
+        in between).  c + q == len: the first token is sampled and the slot is in the state a whole-prompt admission leaves.
+        The sampling state takes the prompt at the first chunk; sample_slots are held from the first chunk and admitted with the
+        last.  Prompt logprobs are gathered over the chunks and handed over after the last; a request that asks for them gets
+        no saving from a hit: its cached rows are computed again (their K/V is NOT written: slot_mapping -1).  c > 0 for a
+        slot that is not prefilling needs a block table brought by the request.  ValueError, nothing enqueued, on any breach."""
+        r = self._normalise_admission(slot, prompt, block_table, num_prompt_tokens, prompt_logprobs,
+                                      [int(c) for c in sample_slots], num_computed_tokens, token_chunk_size)
+        self._check_sample_slots(r.fresh_slots)
+        self._prompt_pass_one(r)
+        if sync:
+            self._sync()
+
+    def _sync(self) -> None:
+        if self.device.type == "cuda":
+            torch.cuda.synchronize()
+
+    def _prompt_pass_one(self, r) -> None:
+        cfg, dev, b = self.cfg, self.device, r.slot
+        if r.table is not None:
+            self.set_block_table(b, r.table)
+        T, ctx = r.rows, r.c + r.q
+        S = prefill_splits([T], [ctx], cfg.num_key_value_heads, cfg.num_attention_heads // cfg.num_key_value_heads)
+        if S == 1:
+            if self._prefill_scratch is None or self._prefill_scratch.T < T:
+                self._prefill_scratch = Scratch(cfg, T, 1, T, n_splits_for(T), dev, logits_rows=1)
+            s = self._prefill_scratch
+        else:   # the Scratch of a pass is sized with the splits of that pass
+            if self._prefix_scratch is None or self._prefix_scratch[0] != S or self._prefix_scratch[1].T < T:
+                self._prefix_scratch = (S, Scratch(cfg, T, 1, T, S, dev, logits_rows=1))
+            s = self._prefix_scratch[1]
+        ids = torch.tensor(r.tokens[r.first:ctx], dtype=torch.int64, device=dev)
+        pos = torch.arange(r.first, ctx, dtype=torch.int64, device=dev)
+        md = AttentionMetadata(self._write_slots(r, pos), self.block_tables[b:b + 1].contiguous(),
+                               torch.tensor([ctx], dtype=torch.int32, device=dev),
+                               torch.tensor([0, T], dtype=torch.int32, device=dev), T, S)
+        hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False, **self._kv_fw)
+        self._finish_prompt_pass([r], hs, [0, T], s)
+
+    def _write_slots(self, r, pos: torch.Tensor) -> torch.Tensor:
+        """slot_mapping of a request's rows: rows in front of its computed count (re-computed for the prompt logprobs only) write
+        nothing -- their blocks may be shared with running sequences."""
+        slots = self._slots_for(r.slot, pos)
+        return slots if r.first == r.c else torch.where(pos < r.c, torch.full_like(slots, -1), slots)
+
+    def _normalise_admission(self, b: int, prompt: Sequence[int], table, npt, plp, extra, c, q):
+        """One request of an admission call, checked against the slot's state (nothing enqueued, ValueError on a breach):
+        slot, tokens, T; c valid tokens, q tokens computed now, first: the first row of the pass (< c only for prompt logprobs);
+        rows = c + q - first; rec: the slot's record when this call continues a chunked prefill; terminal: the first token
+        follows; fresh_slots: the slots that must be empty."""
         if not 0 <= b < self.B:
             raise ValueError(f"slot {b} outside the captured batch of {self.B}")
-        if self._len_ub[b] != 0:
+        rec = (self._prefilling or {}).get(b)
+        tokens, T = [int(t) for t in prompt], len(prompt)
+        if rec is None and not self._is_empty(b):
             raise ValueError(f"slot {b} is occupied; free_slot() it first")
-        sample_slots = [int(c) for c in sample_slots]
-        self._check_sample_slots([b] + sample_slots)
-        if num_prompt_tokens is not None and not 1 <= num_prompt_tokens <= len(prompt):
-            raise ValueError(f"num_prompt_tokens {num_prompt_tokens} outside 1..{len(prompt)}")
-        self._check_num_top(prompt_logprobs)
-        if block_table is not None:
-            self.set_block_table(b, block_table)
-        T = len(prompt)
-        if T < 1 or T + 1 > min(self._capacity[b], self.max_model_len):
-            raise ValueError(f"prompt of {T} tokens does not fit slot {b} (capacity {self._capacity[b]}, "
-                             f"max_model_len {self.max_model_len})")
-        if self._prefill_scratch is None or self._prefill_scratch.T < T:
-            self._prefill_scratch = Scratch(cfg, T, 1, T, n_splits_for(T), dev, logits_rows=1)
-        s = self._prefill_scratch
-        ids = torch.tensor(prompt, dtype=torch.int64, device=dev)
-        pos = torch.arange(T, dtype=torch.int64, device=dev)
-        slots = self._slots_for(b, pos)
-        md = AttentionMetadata(slots, self.block_tables[b:b + 1].contiguous(),
-                               torch.tensor([T], dtype=torch.int32, device=dev),
-                               torch.tensor([0, T], dtype=torch.int32, device=dev), T, n_splits_for(T))
-        hs = self.model.forward(ids, pos, self.kv_caches, md, s, w4a4=False, **self._kv_fw)
-        self.sampling.admit_tokens(b, prompt, num_prompt_tokens)
-        self._admit_samples(b, sample_slots, prompt, num_prompt_tokens)
-        m = 1 + len(sample_slots)
-        self._first_token(hs[T - 1:T] if m == 1 else hs[T - 1:T].expand(m, -1).contiguous(), s, [b] + sample_slots, [T] * m)
-        if prompt_logprobs is not None:
-            self._prompt_logprobs(b, hs[:T - 1], prompt, prompt_logprobs)
-        if sync:
-            torch.cuda.synchronize()
+        if table is not None:
+            table = [int(x) for x in table]
+            self._validate_block_table(table)
+        c = 0 if c is None else int(c)
+        if c < 0 or (q is not None and int(q) < 1):
+            raise ValueError(f"slot {b}: num_computed_tokens {c} / token_chunk_size {q}")
+        if rec is not None:
+            if tokens != rec.tokens:
+                raise ValueError(f"slot {b} is prefilling another token list: free_slot() it first")
+            if c < rec.computed:
+                raise ValueError(f"slot {b}: num_computed_tokens {c} < the {rec.computed} tokens already computed")
+            npt, plp, extra = rec.npt, rec.plp, rec.extra
+        else:
+            if npt is not None and not 1 <= npt <= T:
+                raise ValueError(f"num_prompt_tokens {npt} outside 1..{T}")
+            self._check_num_top(plp)
+            if c > 0 and table is None and self._bt_host[b] is None:
+                raise ValueError(f"slot {b}: num_computed_tokens {c} without a block table that holds them")
+        cap = self._capacity[b] if table is None else len(table) * self.block_size
+        if T < 1 or T + 1 > min(cap, self.max_model_len):
+            raise ValueError(f"prompt of {T} tokens does not fit slot {b} (capacity {cap} tokens, max_model_len "
+                             f"{self.max_model_len})" + ("" if cap else ": the request brought no block table"))
+        c = min(c, T - 1)                      # everything hit: the last token is computed again (model_runner.py:525-531)
+        q = T - c if q is None else min(int(q), T - c)
+        first = c if plp is None else (rec.computed if rec is not None else 0)
+        return SimpleNamespace(slot=b, tokens=tokens, T=T, table=table, npt=npt, plp=plp, extra=list(extra), c=c, q=q,
+                               first=first, rows=c + q - first, rec=rec, terminal=c + q == T,
+                               fresh_slots=([] if rec is not None else [b]) + ([] if rec is not None else list(extra)))
+
+    def _finish_prompt_pass(self, reqs, hs, starts: List[int], scratch) -> None:
+        """Behind the forward: the sampling state takes the prompt (first chunk); a request whose prompt is not through leaves
+        its record and holds its sample slots, the others get their additional samples and the first token; then the prompt
+        logprobs of the rows computed (row at position p predicts token p + 1), gathered per slot until the last chunk."""
+        dev = self.device
+        done = []
+        for i, r in enumerate(reqs):
+            b = r.slot
+            if r.rec is None:
+                self.sampling.admit_tokens(b, r.tokens, r.npt)
+            r.parts = r.rec.parts if r.rec is not None else []
+            if not r.terminal:
+                if self._prefilling is None:
+                    self._prefilling, self._reserved = {}, {}
+                self._prefilling[b] = SimpleNamespace(tokens=r.tokens, computed=r.c + r.q, npt=r.npt, plp=r.plp, extra=r.extra,
+                                                      parts=r.parts)
+                for c in r.extra:
+                    self._reserved[c] = b
+                continue
+            if r.rec is not None:
+                del self._prefilling[b]
+                for c in r.extra:
+                    self._reserved.pop(c, None)
+            self._admit_samples(b, r.extra, r.tokens, r.npt)
+            done.append((i, r))
+        if done:
+            rows, row_slots, row_lens = [], [], []      # one first-token row per request and per additional sample of it
+            for i, r in done:
+                rows += [starts[i + 1] - 1] * (1 + len(r.extra))
+                row_slots += [r.slot, *r.extra]
+                row_lens += [r.T] * (1 + len(r.extra))
+            if len(done) == 1:
+                first_hs = hs[rows[0]:rows[0] + 1]
+                first_hs = first_hs if len(rows) == 1 else first_hs.expand(len(rows), -1).contiguous()
+            else:
+                first_hs = hs[torch.tensor(rows, dtype=torch.int64, device=dev)].contiguous()
+            self._first_token(first_hs, scratch, row_slots, row_lens)
+        self.n_active = len(self.active_slots())
+        for i, r in enumerate(reqs):
+            if r.plp is None:
+                continue
+            n_lp = min(r.c + r.q, r.T - 1) - r.first
+            if r.terminal and r.rec is None:   # the whole prompt in one pass
+                self._prompt_logprobs(r.slot, hs[starts[i]:starts[i] + n_lp], r.tokens, r.plp)
+                continue
+            if n_lp > 0:
+                r.parts.append(self._prompt_logprobs(None, hs[starts[i]:starts[i] + n_lp], r.tokens[r.first:], r.plp))
+            if r.terminal:
+                if self._prompt_results is None:
+                    self._prompt_results = {}
+                self._prompt_results[r.slot] = tuple(torch.cat([p[j] for p in r.parts]) for j in range(4))
+
+    def _is_empty(self, b: int) -> bool:
+        """Nothing holds the slot: no sequence, no partly computed prompt, no reservation for a prefilling request's samples."""
+        return self._len_ub[b] == 0 and not (self._prefilling and b in self._prefilling) and not (self._reserved and b in self._reserved)
+
+    def is_prefilling(self, slot: int) -> bool:
+        return bool(self._prefilling) and slot in self._prefilling
+
+    def num_computed_tokens(self, slot: int) -> int:
+        """Tokens of the partly computed prompt in `slot` whose K/V is valid (0: the slot is not prefilling)."""
+        return self._prefilling[slot].computed if self.is_prefilling(slot) else 0
 
     def _check_sample_slots(self, slots: List[int]) -> None:
         """Every slot of one admission, sample slots included: distinct, inside the batch, empty."""
         if len(set(slots)) != len(slots):
             raise ValueError("a slot appears twice in one admission")
         for c in slots:
-            if not 0 <= c < self.B or self._len_ub[c] != 0:
+            if not 0 <= c < self.B or not self._is_empty(c):
                 raise ValueError(f"slot {c} is not an empty slot of this engine")
 
     def _admit_samples(self, parent: int, sample_slots: Sequence[int], prompt: Sequence[int], num_prompt_tokens: Optional[int]) -> None:
@@ -398,7 +529,7 @@ class QSpecEngine:
             self.gen_lens[b] = 1
             self._len_ub[b] = T + 1
             self._gen_ub[b] = 1
-        self.n_active = sum(1 for v in self._len_ub if v > 0)
+        self.n_active = len(self.active_slots())
 
     def _sample(self, level: int, rows, hs, scratch, probs, token, base_pos, rows_per_seq: int = 1, j_base: int = 0,
                 draw_stream: int = 2, active_lens=None, draft_ids=None, workspace=None, shard_vocab: bool = False, hook=None,
@@ -434,6 +565,10 @@ class QSpecEngine:
         self.gen_lens[slot] = 0
         self._len_ub[slot] = 0
         self._gen_ub[slot] = 0
+        if self._prefilling:                    # a partly computed prompt: its record and the slots held for its samples
+            self._prefilling.pop(slot, None)
+            for c in [c for c, parent in self._reserved.items() if parent == slot or c == slot]:
+                del self._reserved[c]
         for kept in (self._first_probs, self._prompt_results):
             if kept:
                 kept.pop(slot, None)
@@ -450,7 +585,7 @@ class QSpecEngine:
                 self.block_tables[slot].zero_()
                 self._capacity[slot] = 0
             self._bt_host[slot] = None
-        self.n_active = sum(1 for v in self._len_ub if v > 0)
+        self.n_active = len(self.active_slots())
 
     # ------------------------------------------------------------------ block operations and forks (vllm/worker/worker.py, execute_worker)
     def _blocks(self):
@@ -522,7 +657,7 @@ class QSpecEngine:
         (parameters, seed, token-table row, constraint rows and tail).  block_table: the fork's own table (shared blocks plus
         its copy of the last, partially filled one: copy_blocks first); None: the parent's."""
         for b, want in ((src, True), (dst, False)):
-            if not 0 <= b < self.B or (self._len_ub[b] > 0) != want:
+            if not 0 <= b < self.B or (self._len_ub[b] > 0 if want else not self._is_empty(b)) != want:
                 raise ValueError(f"slot {b} is not {'an occupied' if want else 'an empty'} slot of this engine")
         if block_table is None:
             block_table = self._bt_host[src]
@@ -538,7 +673,7 @@ class QSpecEngine:
         self._len_ub[dst], self._gen_ub[dst] = self._len_ub[src], self._gen_ub[src]
         if self._first_probs and src in self._first_probs:
             self._first_probs[dst] = self._first_probs[src]
-        self.n_active = sum(1 for v in self._len_ub if v > 0)
+        self.n_active = len(self.active_slots())
 
     # ------------------------------------------------------------------ logprobs (sampler.py:284, :861-879, :882 ff.)
     @staticmethod
@@ -611,9 +746,10 @@ class QSpecEngine:
             self._plp_logits = torch.empty(R, self.cfg.vocab_size, dtype=torch.float16, device=self.device)
         return self.model.compute_logits(hs, SimpleNamespace(logits=self._plp_logits))
 
-    def _prompt_logprobs(self, slot: int, hs, prompt: Sequence[int], num_top: int) -> None:
+    def _prompt_logprobs(self, slot: Optional[int], hs, prompt: Sequence[int], num_top: int):
         """hs: the hidden rows 0 .. T-2 of the prompt in `slot` (row t predicts prompt[t + 1]): lm_head in chunks, logprobs
-        from the raw logits -- no temperature, penalties or constraints --, results kept for take_prompt_logprobs(slot)."""
+        from the raw logits -- no temperature, penalties or constraints --, results kept for take_prompt_logprobs(slot).
+        slot None (one chunk of a prompt, `prompt` starting at the chunk's first row): the results are returned instead."""
         rows, R = hs.shape[0], self.PROMPT_LOGPROB_ROWS
         ids = torch.tensor(list(prompt[1:]), dtype=torch.int64, device=self.device)
         (lp, rank, top, tlp), host, need = self._logprob_buffers(rows, num_top)
@@ -622,9 +758,12 @@ class QSpecEngine:
             ops.token_logprobs_from_logits(self._prompt_logits(hs[a:e]), ids[a:e], num_top, lp[a:e], rank[a:e],
                                            top[a * num_top:e * num_top] if num_top else None,
                                            tlp[a * num_top:e * num_top] if num_top else None)
+        got = self._read_logprobs(host, need, (rows,), num_top)
+        if slot is None:
+            return got
         if self._prompt_results is None:
             self._prompt_results = {}
-        self._prompt_results[slot] = self._read_logprobs(host, need, (rows,), num_top)
+        self._prompt_results[slot] = got
 
     def take_prompt_logprobs(self, slot: int):
         """The prompt logprobs of the request admitted into `slot` with prompt_logprobs set -- host tensors (logprob [T-1],
@@ -654,7 +793,7 @@ class QSpecEngine:
         allowed token is a single-token bad word -- or, with min_tokens, a stop id)."""
         self.sampling.set(slot, temperature, top_k, top_p, seed, min_p, presence_penalty, frequency_penalty, repetition_penalty,
                           min_tokens, stop_token_ids, logit_bias, allowed_token_ids, bad_words_token_ids,
-                          occupied=self._len_ub[slot] > 0)
+                          occupied=not self._is_empty(slot))
 
     def _process(self, logits, out, rows_per_seq: int, j_base: int, draft_ids, active_lens, slot_ids=None,
                  constrained: Optional[bool] = None):
@@ -685,7 +824,8 @@ class QSpecEngine:
             raise ValueError("block id outside the KV cache")
 
     def active_slots(self) -> List[int]:
-        return [b for b in range(self.B) if self._len_ub[b] > 0]
+        """Slots that hold a request: running sequences and partly computed prompts."""
+        return [b for b in range(self.B) if self._len_ub[b] > 0 or (self._prefilling and b in self._prefilling)]
 
     def sync_lens(self) -> None:
         """Make the host-side length bounds exact (one small device read)."""
@@ -813,6 +953,8 @@ class QSpecEngine:
         return None
 
     def _set_participants(self, participants: Optional[Sequence[int]]) -> List[int]:
+        if participants is not None and self._prefilling and any(b in self._prefilling for b in participants):
+            raise ValueError(f"slot {[b for b in participants if b in self._prefilling]}: the prompt is only partly computed")
         want = [1] * self.B if participants is None else [1 if b in participants else 0 for b in range(self.B)]
         if want != self._mask_host:
             self.step_mask.copy_(torch.tensor(want, dtype=torch.int32), non_blocking=False)

@@ -98,6 +98,13 @@ class SamplingParams:
 class SequenceData:
     prompt_token_ids: List[int]
     output_token_ids: List[int] = field(default_factory=list)
+    _num_computed_tokens: int = 0        # tokens whose K/V an earlier chunk of the prompt has written (vllm/sequence.py)
+
+    def get_num_computed_tokens(self) -> int:
+        return self._num_computed_tokens
+
+    def update_num_computed_tokens(self, num_new_computed_tokens: int) -> None:
+        self._num_computed_tokens += num_new_computed_tokens
 
     def get_len(self):
         return len(self.prompt_token_ids) + len(self.output_token_ids)
@@ -122,6 +129,7 @@ class SequenceGroupMetadata:
     sampling_params: Optional[SamplingParams] = None
     do_sample: bool = True
     token_chunk_size: Optional[int] = None
+    computed_block_nums: Optional[List[int]] = None       # prefix caching: leading blocks whose K/V is already valid
 
 
 @dataclass
@@ -705,15 +713,47 @@ class SpecDecodeWorker:
             return group.bound[seq_id]
         return self._slots[rid]
 
+    def _prompt_window(self, s) -> Tuple[int, int, bool]:
+        """(context, q, terminal) of a prompt group, as the reference's model runner computes them (model_runner.py:488-590):
+        context tokens have valid K/V -- earlier chunks (SequenceData.get_num_computed_tokens) or a prefix-cache hit
+        (computed_block_nums) --, the pass computes the q tokens behind them, terminal: it reaches the end of the token list.
+        A hit that covers the whole chunk leaves its last token to compute."""
+        _, data = self._only_seq(s)
+        total = data.get_len()
+        get = getattr(data, "get_num_computed_tokens", None)
+        context = int(get()) if get is not None else 0
+        seq_len = min(total, context + (getattr(s, "token_chunk_size", None) or total))
+        blocks = getattr(s, "computed_block_nums", None) or ()
+        hit = len(blocks) * self.engine.block_size if blocks else 0
+        if context < hit < seq_len:
+            context = hit
+        elif hit >= seq_len:
+            context = seq_len - 1
+        return context, seq_len - context, seq_len == total
+
     def _admit(self, prompts: List[SequenceGroupMetadata], prompt_logprobs: bool = False) -> List[int]:
         """Prompts (or preempted requests coming back for recomputation) take the first free slots; their prompt pass
         is ONE varlen forward (engine.add_sequences_to); prompt_logprobs: hand the requests' SamplingParams.prompt_logprobs
         to it (disable_logprobs=False, on the rank that returns the outputs).  The engine validates every slot, prompt and block table
         before its first forward; should the admission still fail half-way (several prompt passes, one raising), the
-        slots it had occupied are given back, so that worker and engine never disagree about which slots are free."""
-        counts = [self._num_samples(s) for s in prompts]   # (a request sampling m sequences takes m slots)
+        slots it had occupied are given back, so that worker and engine never disagree about which slots are free.
+        Prefix hits and chunked prefill: every prompt is translated by _prompt_window; a request whose slot holds a partly
+        computed prompt with exactly the tokens the scheduler counts continues in it, any other known request starts over.
+        The new engine keywords are used only when some request needs them."""
+        windows = [self._prompt_window(s) for s in prompts]
+        for s, (_, _, terminal) in zip(prompts, windows):
+            if getattr(s, "do_sample", True) and not terminal:
+                raise ValueError(f"request {s.request_id}: do_sample on a prompt chunk that does not end the prompt")
+        prefilling = getattr(self.engine, "is_prefilling", None)
+        resumed = []
         for s in prompts:
-            if s.request_id in self._slots:          # recomputation: start over
+            slot = self._slots.get(s.request_id)
+            get = getattr(self._only_seq(s)[1], "get_num_computed_tokens", None)
+            resumed.append(slot is not None and prefilling is not None and prefilling(slot) and get is not None
+                           and int(get()) == self.engine.num_computed_tokens(slot))
+        counts = [0 if r else self._num_samples(s) for s, r in zip(prompts, resumed)]   # (a request sampling m sequences takes m slots)
+        for s, r in zip(prompts, resumed):
+            if s.request_id in self._slots and not r:          # recomputation: start over
                 self._release(s.request_id)
         taken = self._taken_slots()
         free = [b for b in range(self.max_num_seqs) if b not in taken]
@@ -723,12 +763,18 @@ class SpecDecodeWorker:
                                f"max_num_seqs={self.max_num_seqs} are running")
         it = iter(free)
         slots, samples = [], []
-        for m in counts:                             # the request's own slot, then those of its additional samples
+        for s, m in zip(prompts, counts):            # the request's own slot, then those of its additional samples
+            if m == 0:                               # (a resumed request keeps what it holds)
+                group = self._group(s.request_id)
+                slots.append(self._slots[s.request_id])
+                samples.append(list(group.slots[1:]) if group is not None else [])
+                continue
             slots.append(next(it))
             samples.append([next(it) for _ in range(m - 1)])
+        fresh = [b for b, extra, r in zip(slots, samples, resumed) if not r for b in [b, *extra]]
         toks, tables, npts, plps = [], [], [], []
         try:
-            for s, b in zip(prompts, slots):
+            for s, b, r, (_, _, terminal) in zip(prompts, slots, resumed, windows):
                 seq_id, data = self._only_seq(s)
                 toks.append(data.get_token_ids())
                 tables.append(s.block_tables.get(seq_id) if s.block_tables else None)
@@ -738,25 +784,32 @@ class SpecDecodeWorker:
                 lp = self._logit_processor_args(sp)
                 lp.update(self._token_constraint_args(sp))
                 extra.update(lp)
-                self.engine.set_sampling_params(b, getattr(sp, "temperature", 0.0) or 0.0, getattr(sp, "top_k", -1) or -1,
-                                                getattr(sp, "top_p", 1.0) if sp is not None else 1.0, **extra)
+                if not r:   # (they belong to the request: a resumed one has them since its first chunk)
+                    self.engine.set_sampling_params(b, getattr(sp, "temperature", 0.0) or 0.0, getattr(sp, "top_k", -1) or -1,
+                                                    getattr(sp, "top_p", 1.0) if sp is not None else 1.0, **extra)
                 # recomputation: prompt + outputs come back as one token list; penalties and min_tokens tell them apart
                 # (nothing else does: a request without them is admitted exactly as before)
                 npts.append(len(data.get_prompt_token_ids()) if lp and data.get_output_len() else None)
-                plps.append(getattr(sp, "prompt_logprobs", None) if prompt_logprobs and s.do_sample else None)
+                # (a chunk that does not end the prompt never samples; its rows still belong to the prompt's logprobs)
+                plps.append(getattr(sp, "prompt_logprobs", None) if prompt_logprobs and (s.do_sample or not terminal) else None)
             kw = {}   # (each only when needed: an engine double need not know the keywords)
             if any(n is not None for n in npts):
                 kw["num_prompt_tokens"] = npts
             if any(n is not None for n in plps):
                 kw["prompt_logprobs"] = plps
-            if any(samples):
-                kw["sample_slots"] = samples
+            if any(e for e, r in zip(samples, resumed) if not r):
+                kw["sample_slots"] = [[] if r else e for e, r in zip(samples, resumed)]
+            if any(c > 0 or not terminal for c, _, terminal in windows):
+                kw["num_computed_tokens"] = [c for c, _, _ in windows]
+                kw["token_chunk_sizes"] = [q for _, q, _ in windows]
             self.engine.add_sequences_to(slots, toks, tables, **kw)
         except Exception:
-            for b in slots + [c for extra in samples for c in extra]:
+            for b in fresh:
                 self.engine.free_slot(b)
             raise
-        for s, slot, extra in zip(prompts, slots, samples):
+        for s, slot, extra, r in zip(prompts, slots, samples, resumed):
+            if r:
+                continue
             self._slots[s.request_id] = slot
             seq_id = self._only_seq(s)[0]
             self._request_id_seq_id_mapping[s.request_id].add(seq_id)
@@ -878,6 +931,36 @@ class SpecDecodeWorker:
                                            "without hand-offs (results invalid)")
         return out
 
+    def _prefill_rows(self, sgml, prompts: List[int], tokens: List[int], more: Dict[int, list], real: Dict[int, tuple],
+                      prompt_real: Dict[int, list]) -> None:
+        """The prompt rows `prompts` of a batch: one prompt pass (_admit), then per row whose pass ended its prompt the first
+        token (tokens[i]), the additional samples (more[i]) and, with real logprobs, their entries (real[i], prompt_real[i]: the
+        WHOLE prompt's, gathered over its chunks).  A chunk that does not end its prompt leaves its row as it is."""
+        ended = [i for i in prompts if self._prompt_window(sgml[i])[2]]   # (read before the pass)
+        slots = dict(zip(prompts, self._admit([sgml[i] for i in prompts], prompt_logprobs=self._real_logprobs)))
+        first = self.engine.gen_tokens[:, 0].cpu()
+        self._check_out_of_cycle_errors("the prompt pass")
+        for i in ended:
+            tokens[i] = int(first[slots[i]])
+            group = self._group(sgml[i].request_id)
+            if group is not None:       # the samples' first tokens: what binds their sequence ids on the next step
+                group.first = [int(first[b]) for b in group.slots]
+                more[i] = [[t, None] for t in group.first[1:]]
+        self.scorer_calls += 1          # one scorer call for the prompt batch, as in the reference
+        if self._real_logprobs and ended:
+            real.update(self._token_logprobs("first", [sgml[i] for i in ended], ended, [slots[i] for i in ended], tokens))
+            for i in more:              # (per sample, as for a single sequence)
+                sample_slots = self._group(sgml[i].request_id).slots[1:]
+                n_top = self._num_logprobs(sgml[i])
+                lp, rank, top, tlp = (t.tolist() for t in self.engine.token_logprobs(
+                    "first", sample_slots, [t for t, _ in more[i]], n_top))
+                for j, entry in enumerate(more[i]):
+                    entry[1] = (rank[j], lp[j], top[j][:n_top], tlp[j][:n_top])
+            for i in ended:
+                got = self.engine.take_prompt_logprobs(slots[i])
+                if got is not None:
+                    prompt_real[i] = self._prompt_logprob_dicts(sgml[i], got)
+
     def _run_no_spec(self, req: ExecuteModelRequest, skip_proposer: bool) -> List[SamplerOutput]:
         """:666-720.  Prompts: W4A16 prefill, first token sampled by the target.  Decode sequences with speculation off
         for this step: the scorer alone, one token each.  A batch may hold both (prompts first, as vLLM orders them).
@@ -893,29 +976,7 @@ class SpecDecodeWorker:
         decodes = [i for i, s in enumerate(sgml) if not s.is_prompt]
         dslots = self._decode_slots([sgml[i] for i in decodes])     # before admissions: validates the running ones
         if prompts:
-            slots = self._admit([sgml[i] for i in prompts], prompt_logprobs=self._real_logprobs)
-            first = self.engine.gen_tokens[:, 0].cpu()
-            self._check_out_of_cycle_errors("the prompt pass")
-            for i, slot in zip(prompts, slots):
-                tokens[i] = int(first[slot])
-                group = self._group(sgml[i].request_id)
-                if group is not None:       # the samples' first tokens: what binds their sequence ids on the next step
-                    group.first = [int(first[b]) for b in group.slots]
-                    more[i] = [[t, None] for t in group.first[1:]]
-            self.scorer_calls += 1          # one scorer call for the prompt batch, as in the reference
-            if self._real_logprobs:
-                real.update(self._token_logprobs("first", [sgml[i] for i in prompts], prompts, slots, tokens))
-                for i in more:              # (per sample, as for a single sequence)
-                    sample_slots = self._group(sgml[i].request_id).slots[1:]
-                    n_top = self._num_logprobs(sgml[i])
-                    lp, rank, top, tlp = (t.tolist() for t in self.engine.token_logprobs(
-                        "first", sample_slots, [t for t, _ in more[i]], n_top))
-                    for j, entry in enumerate(more[i]):
-                        entry[1] = (rank[j], lp[j], top[j][:n_top], tlp[j][:n_top])
-                for i, slot in zip(prompts, slots):
-                    got = self.engine.take_prompt_logprobs(slot)
-                    if got is not None:
-                        prompt_real[i] = self._prompt_logprob_dicts(sgml[i], got)
+            self._prefill_rows(sgml, prompts, tokens, more, real, prompt_real)
         if decodes:
             tok = self._no_spec_step(dslots)
             for i, slot in zip(decodes, dslots):
@@ -1010,13 +1071,26 @@ class SpecDecodeWorker:
             raise ValueError(f"num_lookahead_slots = {num_lookahead_slots}, but the cycle was captured for "
                              f"num_speculative_tokens = {k} (SpeculativeConfig.num_speculative_tokens)")
         groups = req.seq_group_metadata_list
-        if any(s.is_prompt for s in groups):
-            raise NotImplementedError("prompt chunks inside a speculative step (chunked prefill) are not scheduled onto "
-                                      "this worker: vLLM sends prompt-only batches with num_lookahead_slots == 0")
         sgml, owner = self._sequence_rows(groups)    # one row per sequence
-        slots = self._decode_slots(sgml)
-        spec = [i for i, s in enumerate(sgml) if s.num_speculative_tokens != 0]
-        nospec = [i for i, s in enumerate(sgml) if s.num_speculative_tokens == 0]
+        # Prompt chunks scheduled into a speculative step (chunked prefill; spec_decode_worker.py:484-537, 818-825): their own
+        # W4A16 forward in front of the cycle, which the proposer never sees (:827).  A prompt's row is [first token, -1 x k]
+        # when the chunk ends the prompt and all -1 otherwise; the request joins the cycle with the next step.
+        prompts = [i for i, s in enumerate(sgml) if s.is_prompt]
+        decodes = [i for i, s in enumerate(sgml) if not s.is_prompt]
+        slots: List[Optional[int]] = [None] * len(sgml)
+        for i, b in zip(decodes, self._decode_slots([sgml[i] for i in decodes])):   # before admissions: validates the running ones
+            slots[i] = b
+        rows = [[VLLM_INVALID_TOKEN_ID] * (k + 1) for _ in sgml]
+        more: Dict[int, list] = {}
+        first_real: Dict[int, tuple] = {}
+        prompt_real: Dict[int, list] = {}
+        if prompts:
+            first_tokens = [VLLM_INVALID_TOKEN_ID] * len(sgml)
+            self._prefill_rows(sgml, prompts, first_tokens, more, first_real, prompt_real)
+            for i in prompts:
+                rows[i][0] = first_tokens[i]
+        spec = [i for i in decodes if sgml[i].num_speculative_tokens != 0]
+        nospec = [i for i in decodes if sgml[i].num_speculative_tokens == 0]
         req.w4a4 = True                                   # :799
         self.proposer_calls += k
         scorer_req = req.clone(groups)                    # mqa_scorer.py:65: clone drops w4a4 -> W4A16
@@ -1027,22 +1101,31 @@ class SpecDecodeWorker:
         self.engine.step(participants=spec_slots)
         out = self._read_cycle()
         self.engine.note_emitted([int((out[b] != -1).sum()) if b in spec_slots else 0 for b in range(out.shape[0])])
-        rows = [[VLLM_INVALID_TOKEN_ID] * (k + 1) for _ in sgml]
         for i in spec:
             rows[i] = out[slots[i]].tolist()
         cycle_real = None
         if self._real_logprobs and spec:
             cycle_real = self.engine.token_logprobs("cycle", spec_slots, [[max(t, 0) for t in rows[i]] for i in spec],
                                                     max(self._num_logprobs(sgml[i]) for i in spec))
-        riders = None
+        riders = dict(first_real) or None
         if nospec:
             tok = self._no_spec_step([slots[i] for i in nospec])
             for i in nospec:
                 rows[i][0] = tok[slots[i]]
             if self._real_logprobs:
-                riders = self._token_logprobs("no_spec", [sgml[i] for i in nospec], nospec, [slots[i] for i in nospec],
-                                              [r[0] for r in rows])
-        return self._regroup(self._create_output_sampler_list(sgml, rows, k, slots, spec, cycle_real, riders), owner, len(groups))
+                riders = {**first_real, **self._token_logprobs("no_spec", [sgml[i] for i in nospec], nospec,
+                                                               [slots[i] for i in nospec], [r[0] for r in rows])}
+        outs = self._create_output_sampler_list(sgml, rows, k, slots, spec, cycle_real, riders)
+        if outs:   # step 0 carries what only a prompt row has: the additional samples and the prompt's logprobs
+            for i, extra in more.items():
+                seq_id = self._only_seq(sgml[i])[0]
+                for t, entry in extra:
+                    rank, lp, top, tlp = entry if entry is not None else (-1, 0.0, [], [])
+                    logprobs = create_logprobs_output(t, rank, lp, [v if v >= 0 else None for v in top], tlp)
+                    outs[0].outputs[i].samples.append(SequenceOutput(parent_seq_id=seq_id, output_token=t, logprobs=logprobs))
+            for i, lps in prompt_real.items():
+                outs[0].outputs[i].prompt_logprobs = lps
+        return self._regroup(outs, owner, len(groups))
 
     def _create_output_sampler_list(self, sgml, rows: List[List[int]], k: int, slots: List[int],
                                     spec: Optional[List[int]] = None, cycle_real=None,
