@@ -551,6 +551,54 @@ int qspec_token_constraints_set(uint32_t* deny, int deny_words, int32_t* meta, i
                                 const int32_t* src_words, const int32_t* src_word_lens, int num_words, int bad_words_present,
                                 void* stream);
 
+/* Token guides: guided decoding.  The reference's engine lowers guided_decoding (regex, JSON schema, choice) to an Outlines
+ *   processor at index 0 of logits_processors (vllm/engine/llm_engine.py:1950-2009); its call
+ *   (vllm/model_executor/guided_decoding/outlines_logits_processors.py:34-93) advances a finite automaton over the sequence's
+ *   OUTPUT tokens through a hash chain and adds an fp32 mask -- 0 at the state's allowed ids below vocab, -inf elsewhere -- to
+ *   the fp16 row.  Here the automaton is resident on the device and the masking rides in the pre-pass launch, per ROW: row j is
+ *   masked with the state reached over the outputs the request had before its admission, the committed ones and the in-flight
+ *   d_1 .. d_j (the rule of the bad words; the reference's own MQA scoring hands a processor ONE token list for k + 1 rows).
+ *   A guide is a DFA over token ids: per state a non-empty set of allowed tokens < vocab with a next state each, and a `miss`
+ *   state that any other token leads to.  The guide arena, shared by the slots, per resident state s (states are arena rows):
+ *     guide_allow [max_states, guide_words] uint32, guide_words a multiple of 4 with guide_words * 32 >= vocab: bit v = token v
+ *       is allowed in s;
+ *     guide_rank [max_states, guide_words] int32: the exclusive prefix popcount of the allow row, per word;
+ *     guide_off [max_states] int32, guide_next [max_transitions] int32: the next states (arena rows) of s's allowed tokens,
+ *       ascending by token, start at guide_next[guide_off[s]];
+ *     next(s, t) = bit (t & 31) of allow[s][t >> 5] set ? next[off[s] + rank[s][t >> 5] + popc(allow[s][t >> 5] & ((1 << (t & 31)) - 1))]
+ *                  : miss            -- two dependent loads per token, no search, no [states, vocab] table;
+ *     guide_slots [num_slots, 4] int32: {state after the outputs counted so far, g_len (how many of gen_tokens[slot] those
+ *       are), the guide's miss state, 1 = the slot is guided}.  All zero: the slot is unguided.
+ *   qspec_guide_build (admission, outside the graph): builds the allow and rank rows, the offsets and the transitions of the
+ *     num_states states of one guide from its CSR (row_ptr [num_states + 1] int32, tokens ascending and distinct per state, next
+ *     states local to the guide; VALIDATED BY THE CALLER) at arena rows state_base .. and transitions transition_base .. .  Rows
+ *     are row_stride words apart (the arena: row_stride == guide_words); only guide_words words of a row are written.
+ *   qspec_guide_catch_up (head of a guided cycle): state = next*(state, gen_tokens[slot][g_len .. gen_lens[slot])), g_len =
+ *     gen_lens[slot], for every guided slot.  Driven by gen_lens alone, hence idempotent (as qspec_logit_table_catch_up).
+ *   qspec_process_logits_guided: qspec_process_logits_constrained with, in front of its steps, for every row of a guided slot
+ *       x[v] = -inf where v is not allowed in next*(state, d_1 .. d_j)        (SET, where the reference adds -inf: a +inf or
+ *                                                                              NaN logit is -inf here, NaN there);
+ *       x = fp16(fp32(x) + 0.0f) for every element                            (the mask's zeros: -0.0 becomes +0.0).
+ *     Rows of unguided slots get the bits of qspec_process_logits_constrained.  Nothing is written but `out`. */
+int qspec_process_logits_guided(const qspec_half* logits, qspec_half* out, int tokens, int vocab, const uint32_t* tok_table,
+                                int num_slots, const int32_t* slot_ids, const int32_t* active_lens, const qspec_half* repetition,
+                                const qspec_half* frequency, const qspec_half* presence, const int32_t* min_tokens,
+                                const int32_t* gen_base, const int32_t* gen_lens, const int32_t* stop_ids,
+                                const int32_t* num_stop_ids, int stop_ids_per_slot, const int64_t* draft_ids, int draft_rows,
+                                int64_t ids_stride_b, int64_t ids_stride_k, int rows_per_seq, int j_base, const uint32_t* deny,
+                                int deny_words, const int32_t* meta, const int32_t* bias_ids, const float* bias_vals,
+                                const int32_t* words, const int32_t* word_lens, const int32_t* tail, const int64_t* gen_tokens,
+                                int gen_cap, const uint32_t* guide_allow, const int32_t* guide_rank, const int32_t* guide_off,
+                                const int32_t* guide_next, const int32_t* guide_slots, int guide_words, int guide_states,
+                                int guide_transitions, void* stream);
+int qspec_guide_build(uint32_t* guide_allow, int32_t* guide_rank, int32_t* guide_off, int32_t* guide_next, int guide_words,
+                      int row_stride, int vocab, int max_states, int max_transitions, int state_base, int transition_base,
+                      int num_states, int num_transitions, const int32_t* row_ptr, const int32_t* tokens,
+                      const int32_t* next_states, void* stream);
+int qspec_guide_catch_up(int32_t* guide_slots, int num_slots, int vocab, const uint32_t* guide_allow, const int32_t* guide_rank,
+                         const int32_t* guide_off, const int32_t* guide_next, int guide_words, int guide_states,
+                         int guide_transitions, const int64_t* gen_tokens, int gen_cap, const int32_t* gen_lens, void* stream);
+
 /* TypicalAcceptanceSampler.forward(target_with_bonus_probs, bonus_token_ids, draft_probs, draft_token_ids)
  *   vllm/model_executor/layers/typical_acceptance_sampler.py:37-172 (MEDUSA 3.3.1), selected by
  *   draft_token_acceptance_method = "typical_acceptance_sampler" (vllm/spec_decode/spec_decode_worker.py:95-110).

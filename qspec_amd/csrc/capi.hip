@@ -326,7 +326,8 @@ int process_logits(const char* op, bool constrained, const qspec_half* logits, q
                    const int32_t* num_stop_ids, int stop_ids_per_slot, const int64_t* draft_ids, int draft_rows,
                    int64_t ids_stride_b, int64_t ids_stride_k, int rows_per_seq, int j_base, const uint32_t* deny,
                    int deny_words, const int32_t* meta, const int32_t* bias_ids, const float* bias_vals, const int32_t* words,
-                   const int32_t* word_lens, const int32_t* tail, const int64_t* gen_tokens, int gen_cap, void* stream) {
+                   const int32_t* word_lens, const int32_t* tail, const int64_t* gen_tokens, int gen_cap,
+                   const qspec::LpGuide* guide, void* stream) {
     if (tokens < 0) return fail("%s: tokens < 0", op);
     if (tokens == 0) return 0;
     NONNULL(op, logits); NONNULL(op, out); NONNULL(op, tok_table); NONNULL(op, repetition); NONNULL(op, frequency);
@@ -337,6 +338,16 @@ int process_logits(const char* op, bool constrained, const qspec_half* logits, q
         NONNULL(op, word_lens); NONNULL(op, tail); NONNULL(op, gen_tokens);
         if ((int64_t)deny_words * 32 < vocab) return fail("%s: deny_words=%d does not cover vocab=%d", op, deny_words, vocab);
         if (gen_cap < 1) return fail("%s: gen_cap=%d must be >= 1", op, gen_cap);
+    }
+    if (guide) {
+        const void *guide_allow = guide->allow, *guide_rank = guide->rank, *guide_off = guide->off, *guide_next = guide->nxt,
+                   *guide_slots = guide->gslot;   // (the names the header gives them: the messages name the argument)
+        NONNULL(op, guide_allow); NONNULL(op, guide_rank); NONNULL(op, guide_off); NONNULL(op, guide_next);
+        NONNULL(op, guide_slots);
+        if (guide->words % 4 || (int64_t)guide->words * 32 < vocab)
+            return fail("%s: guide_words=%d must be a multiple of 4 that covers vocab=%d", op, guide->words, vocab);
+        if (guide->n_states < 1 || guide->n_trans < 1)
+            return fail("%s: guide_states=%d / guide_transitions=%d must be >= 1", op, guide->n_states, guide->n_trans);
     }
     if (logits == out) return fail("%s: the pass is out of place (logits == out)", op);
     if (vocab < 1) return fail("%s: vocab < 1", op);
@@ -352,12 +363,13 @@ int process_logits(const char* op, bool constrained, const qspec_half* logits, q
     if (j_base + rows_per_seq - 1 > 64) return fail("%s: more than 64 in-flight tokens", op);
     if (!slot_ids && (int64_t)num_slots * rows_per_seq < tokens)
         return fail("%s: num_slots=%d x rows_per_seq=%d does not cover tokens=%d", op, num_slots, rows_per_seq, tokens);
-    qspec::LpArgsC a{};
+    qspec::LpArgsG a{};
     static_cast<qspec::LpArgs&>(a) = qspec::LpArgs{CH(logits), H(out), tok_table, slot_ids, active_lens, CH(repetition),
                                                    CH(frequency), CH(presence), min_tokens, gen_base, gen_lens, stop_ids,
                                                    num_stop_ids, draft_rows > 0 ? draft_ids : nullptr, ids_stride_b, ids_stride_k,
                                                    vocab, rows_per_seq, j_base, num_slots, stop_ids_per_slot};
     if (constrained) a.c = qspec::LpCons{deny, meta, bias_ids, bias_vals, words, word_lens, tail, gen_tokens, gen_cap, deny_words};
+    if (guide) a.g = *guide;
     return finish(op, qspec::process_logits(a, tokens, ST));
 }
 int spec_advance_draft(const char* op, bool embed, int batch, int block_size, int max_blocks_per_seq, int64_t* input_tokens,
@@ -837,7 +849,7 @@ int qspec_process_logits(const qspec_half* logits, qspec_half* out, int tokens, 
     return process_logits("qspec_process_logits", false, logits, out, tokens, vocab, tok_table, num_slots, slot_ids,
                           active_lens, repetition, frequency, presence, min_tokens, gen_base, gen_lens, stop_ids, num_stop_ids,
                           stop_ids_per_slot, draft_ids, draft_rows, ids_stride_b, ids_stride_k, rows_per_seq, j_base, nullptr,
-                          0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream);
+                          0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, stream);
 }
 // Token constraints (include/qspec_hip.h, "token constraints"): vllm/entrypoints/openai/logits_processors.py:10-50 and
 // vllm/logits_process.py:48-119 inside the pre-pass launch.
@@ -854,7 +866,63 @@ int qspec_process_logits_constrained(const qspec_half* logits, qspec_half* out, 
     return process_logits("qspec_process_logits_constrained", true, logits, out, tokens, vocab, tok_table, num_slots, slot_ids,
                           active_lens, repetition, frequency, presence, min_tokens, gen_base, gen_lens, stop_ids, num_stop_ids,
                           stop_ids_per_slot, draft_ids, draft_rows, ids_stride_b, ids_stride_k, rows_per_seq, j_base, deny,
-                          deny_words, meta, bias_ids, bias_vals, words, word_lens, tail, gen_tokens, gen_cap, stream);
+                          deny_words, meta, bias_ids, bias_vals, words, word_lens, tail, gen_tokens, gen_cap, nullptr, stream);
+}
+// Token guides (include/qspec_hip.h, "token guides"): vllm/model_executor/guided_decoding/outlines_logits_processors.py:34-93
+// inside the pre-pass launch, the automaton resident on the device.
+int qspec_process_logits_guided(const qspec_half* logits, qspec_half* out, int tokens, int vocab, const uint32_t* tok_table,
+                                int num_slots, const int32_t* slot_ids, const int32_t* active_lens, const qspec_half* repetition,
+                                const qspec_half* frequency, const qspec_half* presence, const int32_t* min_tokens,
+                                const int32_t* gen_base, const int32_t* gen_lens, const int32_t* stop_ids,
+                                const int32_t* num_stop_ids, int stop_ids_per_slot, const int64_t* draft_ids, int draft_rows,
+                                int64_t ids_stride_b, int64_t ids_stride_k, int rows_per_seq, int j_base, const uint32_t* deny,
+                                int deny_words, const int32_t* meta, const int32_t* bias_ids, const float* bias_vals,
+                                const int32_t* words, const int32_t* word_lens, const int32_t* tail, const int64_t* gen_tokens,
+                                int gen_cap, const uint32_t* guide_allow, const int32_t* guide_rank, const int32_t* guide_off,
+                                const int32_t* guide_next, const int32_t* guide_slots, int guide_words, int guide_states,
+                                int guide_transitions, void* stream) {
+    const qspec::LpGuide g{guide_allow, guide_rank, guide_off, guide_next, guide_slots, guide_words, guide_states, guide_transitions};
+    return process_logits("qspec_process_logits_guided", true, logits, out, tokens, vocab, tok_table, num_slots, slot_ids,
+                          active_lens, repetition, frequency, presence, min_tokens, gen_base, gen_lens, stop_ids, num_stop_ids,
+                          stop_ids_per_slot, draft_ids, draft_rows, ids_stride_b, ids_stride_k, rows_per_seq, j_base, deny,
+                          deny_words, meta, bias_ids, bias_vals, words, word_lens, tail, gen_tokens, gen_cap, &g, stream);
+}
+int qspec_guide_build(uint32_t* guide_allow, int32_t* guide_rank, int32_t* guide_off, int32_t* guide_next, int guide_words,
+                      int row_stride, int vocab, int max_states, int max_transitions, int state_base, int transition_base,
+                      int num_states, int num_transitions, const int32_t* row_ptr, const int32_t* tokens,
+                      const int32_t* next_states, void* stream) {
+    const char* op = "qspec_guide_build";
+    NONNULL(op, guide_allow); NONNULL(op, guide_rank); NONNULL(op, guide_off); NONNULL(op, guide_next); NONNULL(op, row_ptr);
+    NONNULL(op, tokens); NONNULL(op, next_states);
+    if (vocab < 1) return fail("%s: vocab < 1", op);
+    if (guide_words < 4 || guide_words % 4 || guide_words > 8192 || (int64_t)guide_words * 32 < vocab)
+        return fail("%s: guide_words=%d must be a multiple of 4 in 4..8192 that covers vocab=%d", op, guide_words, vocab);
+    if (row_stride < guide_words || row_stride % 4)
+        return fail("%s: row_stride=%d must be a multiple of 4 >= guide_words=%d", op, row_stride, guide_words);
+    if (num_states < 1 || state_base < 0 || (int64_t)state_base + num_states > max_states)
+        return fail("%s: states %d..%d outside the arena's %d", op, state_base, state_base + num_states, max_states);
+    if (num_transitions < 1 || transition_base < 0 || (int64_t)transition_base + num_transitions > max_transitions)
+        return fail("%s: transitions %d..%d outside the arena's %d", op, transition_base, transition_base + num_transitions,
+                    max_transitions);
+    return finish(op, qspec::guide_build(guide_allow, guide_rank, guide_off, guide_next, guide_words, row_stride, vocab, state_base,
+                                         transition_base, num_states, row_ptr, tokens, next_states, num_transitions, ST));
+}
+int qspec_guide_catch_up(int32_t* guide_slots, int num_slots, int vocab, const uint32_t* guide_allow, const int32_t* guide_rank,
+                         const int32_t* guide_off, const int32_t* guide_next, int guide_words, int guide_states,
+                         int guide_transitions, const int64_t* gen_tokens, int gen_cap, const int32_t* gen_lens, void* stream) {
+    const char* op = "qspec_guide_catch_up";
+    if (num_slots < 0) return fail("%s: num_slots < 0", op);
+    if (num_slots == 0) return 0;
+    NONNULL(op, guide_slots); NONNULL(op, guide_allow); NONNULL(op, guide_rank); NONNULL(op, guide_off); NONNULL(op, guide_next);
+    NONNULL(op, gen_tokens); NONNULL(op, gen_lens);
+    if (vocab < 1) return fail("%s: vocab < 1", op);
+    if (gen_cap < 1) return fail("%s: gen_cap=%d must be >= 1", op, gen_cap);
+    if (guide_words % 4 || (int64_t)guide_words * 32 < vocab)
+        return fail("%s: guide_words=%d must be a multiple of 4 that covers vocab=%d", op, guide_words, vocab);
+    if (guide_states < 1 || guide_transitions < 1)
+        return fail("%s: guide_states=%d / guide_transitions=%d must be >= 1", op, guide_states, guide_transitions);
+    const qspec::LpGuide g{guide_allow, guide_rank, guide_off, guide_next, guide_slots, guide_words, guide_states, guide_transitions};
+    return finish(op, qspec::guide_catch_up(num_slots, vocab, guide_slots, g, gen_tokens, gen_cap, gen_lens, ST));
 }
 int qspec_token_constraints_set(uint32_t* deny, int deny_words, int32_t* meta, int32_t* bias_ids, float* bias_vals,
                                 int32_t* words, int32_t* word_lens, int num_slots, int vocab, int slot,

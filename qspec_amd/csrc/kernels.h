@@ -261,7 +261,23 @@ struct LpCons {
     int gen_cap, deny_words;
 };
 struct LpArgsC : LpArgs { LpCons c; };
-int process_logits(const LpArgsC& a, int T, hipStream_t st);
+// token guides (guided decoding: a DFA over token ids per slot) in front of the token constraints, inside the same launch: the
+// arena and the per-slot state sampler.hip describes ("Token guides"); allow == NULL: none
+struct LpGuide {
+    const uint32_t* allow;        // [states, words] bit v of row s: token v is allowed in state s
+    const int32_t* rank;          // [states, words] exclusive prefix popcount of the allow row, per word
+    const int32_t* off;           // [states] where the state's transitions start in nxt
+    const int32_t* nxt;           // next states, ordered by (state, token)
+    const int32_t* gslot;         // [nslots, 4] {state, g_len, miss state, guided}
+    int words, n_states, n_trans; // row width in words (a multiple of 4, words * 32 >= V); arena sizes (the walk clamps to them)
+};
+struct LpArgsG : LpArgsC { LpGuide g; };
+int process_logits(const LpArgsG& a, int T, hipStream_t st);
+int guide_build(uint32_t* allow, int32_t* rank, int32_t* off, int32_t* nxt, int words, int row_stride, int V, int state_base,
+                int trans_base, int n_states, const int32_t* row_ptr, const int32_t* tokens, const int32_t* next, int n_trans,
+                hipStream_t st);
+int guide_catch_up(int B, int V, int32_t* gslot, const LpGuide& g, const int64_t* gen_tokens, int gen_cap,
+                   const int32_t* gen_lens, hipStream_t st);
 int token_constraints_set(uint32_t* deny, int deny_words, int32_t* meta, int32_t* bias_ids, float* bias_vals, int32_t* words,
                           int32_t* word_lens, int V, int slot, const int64_t* allowed, int n_allowed, const int64_t* banned,
                           int n_banned, const int32_t* src_bias_ids, const float* src_bias_vals, int n_bias,

@@ -922,8 +922,41 @@ __device__ __forceinline__ f16 lp_element(f16 x, int v, uint32_t w, const LpRow&
 #define QS_TC_MAX_WORDS 32     // QS_MAX_BAD_WORDS
 #define QS_TC_WORD_LEN 8       // QS_MAX_BAD_WORD_LEN
 // LpCons, LpArgsC (kernels.h): that per-slot state, behind the arguments of the plain pass
-template <bool C> struct LpArgsOf { typedef LpArgs type; };
-template <> struct LpArgsOf<true> { typedef LpArgsC type; };
+template <bool C, bool G = false> struct LpArgsOf { typedef LpArgs type; };
+template <> struct LpArgsOf<true, false> { typedef LpArgsC type; };
+template <> struct LpArgsOf<true, true> { typedef LpArgsG type; };
+// Token guides (guided decoding): the reference's engine lowers guided_decoding (regex, JSON schema, choice) to an Outlines
+// processor at index 0 of logits_processors (vllm/engine/llm_engine.py:1950-2009) whose call
+// (vllm/model_executor/guided_decoding/outlines_logits_processors.py:34-93) advances a finite automaton over the sequence's OUTPUT
+// tokens and adds an fp32 mask, 0 at the state's allowed ids and -inf elsewhere, to the fp16 row.  Here the automaton lives on
+// the device, because row j's state depends on the in-flight draft tokens d_1 .. d_j.  The guide arena, per resident state s:
+//   allow [states, words] u32: bit v = token v is allowed in s (the geometry of deny; words a multiple of 4);
+//   rank  [states, words] i32: the exclusive prefix popcount of the allow row, per word;
+//   off   [states] i32 and nxt[] i32: the next states of s's allowed tokens, ascending by token, start at nxt[off[s]];
+//   next(s, t) = allow[s][t >> 5] bit (t & 31) ? nxt[off[s] + rank[s][t >> 5] + popc(allow[s][t >> 5] & ((1 << (t & 31)) - 1))] : miss
+// -- two dependent round trips per token (allow, rank and off are independent loads), no search, no dense [S, V] table.  States
+// are arena rows: a guide's states are contiguous and its nxt entries are stored as arena rows, so a walk needs no base.
+//   gslot [nslots, 4] i32: {state after the outputs counted so far, g_len, the guide's miss state, 1 = the slot is guided}.
+// INVARIANT (the twin of counted_len's above): catch-up is driven by gen_lens alone -- it advances state over
+// gen_tokens[slot][g_len .. gen_len) and sets g_len = gen_len -- so it is idempotent, and a cycle re-run by recover() needs no
+// rollback: spec_snapshot(restore) brings gen_lens back to g_len and the re-run's catch-up finds nothing to walk.  Outputs a
+// re-admitted request had before its admission are walked on the host at admission (g_len = 0 then).
+__device__ __forceinline__ int guide_next(const LpGuide& g, int V, int s, int64_t t, int miss) {
+    if (t < 0 || t >= V || s < 0 || s >= g.n_states) return miss;
+    const size_t wi = (size_t)s * g.words + (size_t)(t >> 5);
+    const uint32_t aw = g.allow[wi];      // first round trip: three independent loads
+    const int r = g.rank[wi];
+    const int o = g.off[s];
+    const uint32_t bit = 1u << (t & 31);
+    if (!(aw & bit)) return miss;
+    const int i = o + r + __builtin_popcount(aw & (bit - 1u));
+    if (i < 0 || i >= g.n_trans) return miss;
+    return g.nxt[i];                      // second round trip
+}
+template <bool G> __device__ __forceinline__ int* guide_state_word() {   // (LDS of the guided instantiation alone)
+    __shared__ int s_gstate;
+    return &s_gstate;
+}
 // grid (chunks of 2048 logits, rows): 16-byte loads of the logits and of the table words, 16-byte stores; a row is wave-uniform
 // in everything but the element itself.  About 8 B of traffic per element (2 + 4 read, 2 written).
 // C (token constraints, in front of the pipeline above): x[id] = fp16(x[id] + bias); deny bits and matched multi-token bad words
@@ -933,8 +966,16 @@ template <> struct LpArgsOf<true> { typedef LpArgsC type; };
 // workgroup's chunk are applied to the chunk staged in LDS (no workgroup stages anything when none does: __syncthreads_or).
 // Every workgroup of a row resolves the bad-word matches itself: threads 0..6 fetch the row's last 7 tokens (in-flight, then
 // committed, then the pre-admission tail), threads 0..31 compare one word each.  Nothing is written but `out`.
-template <bool C>
-__global__ __launch_bounds__(256) void process_logits_kernel(typename LpArgsOf<C>::type a) {
+// G (token guides, in front of C; its own instantiation: <false> and <true> are the kernels they were): a guided row's workgroup
+// resolves its state itself -- one lane of the second wave walks the row's j in-flight tokens from gslot[slot].state (at most
+// QS_LP_MAX_INFLIGHT steps of two round trips, issued behind the element loads, so they overlap) and broadcasts it through LDS;
+// then every thread reads one byte of allow[state] beside its deny byte: deny |= ~allow.  Every element of a guided row gets
+// the fp32 zero the reference's scores.add_(mask) adds at allowed ids (-0.0 becomes +0.0), on the element as loaded.  The
+// reference's order is guide, bias, allowed, bad words: the zero is added in front of the bias as there, and the guide's -inf
+// assignments commute with a finite bias like the others, so they land with the deny bits.  Rows of unguided slots get the bits
+// of the <true> instantiation.
+template <bool C, bool G = false>
+__global__ __launch_bounds__(256) void process_logits_kernel(typename LpArgsOf<C, G>::type a) {
     __shared__ int64_t s_inflight[QS_LP_MAX_INFLIGHT];
     __shared__ int32_t s_stop[QS_LP_MAX_STOP];
     const int t = blockIdx.y, seq = t / a.rows_per_seq, j = a.j_base + t % a.rows_per_seq;
@@ -959,7 +1000,11 @@ __global__ __launch_bounds__(256) void process_logits_kernel(typename LpArgsOf<C
         __shared__ f16 s_x[QS_LP_CHUNK];
         const int tid = threadIdx.x;
         const int4 meta = *reinterpret_cast<const int4*>(a.c.meta + 4 * slot);
-        const bool deny_on = on && (meta.x & 1), zero_add = on && (meta.x & 2);
+        const bool deny_on = on && (meta.x & 1);
+        const bool zero_add = on && (meta.x & 2);
+        int4 gs = int4{0, 0, 0, 0};
+        if constexpr (G) gs = *reinterpret_cast<const int4*>(a.g.gslot + 4 * slot);
+        const bool guided = G && on && gs.w != 0;
         const int n_bias = on ? min(max(meta.y, 0), QS_TC_MAX_BIAS) : 0;
         const int n_words = on ? min(max(meta.z, 0), QS_TC_MAX_WORDS) : 0;
         const bool vec = V % 8 == 0;
@@ -986,6 +1031,14 @@ __global__ __launch_bounds__(256) void process_logits_kernel(typename LpArgsOf<C
             deny = reinterpret_cast<const uint8_t*>(a.c.deny + (size_t)slot * a.c.deny_words)[v0 >> 3];
         }
         if (!deny_on) deny = 0u;
+        if constexpr (G) {   // the row's state: gslot's, advanced over the in-flight tokens d_1 .. d_j
+            if (guided && tid == 64) {
+                int s = gs.x;
+                const int n = a.draft_ids ? min(j, QS_LP_MAX_INFLIGHT) : 0;
+                for (int i = 0; i < n; i++) s = guide_next(a.g, V, s, a.draft_ids[slot * a.di_sb + i * a.di_sk], gs.z);
+                *guide_state_word<G>() = min(max(s, 0), a.g.n_states - 1);
+            }
+        }
         // logit_bias entries of this thread (two at most) that fall into the chunk
         int bid[2]; float bval[2];
 #pragma unroll
@@ -1019,6 +1072,16 @@ __global__ __launch_bounds__(256) void process_logits_kernel(typename LpArgsOf<C
             wl = min(max(a.c.word_lens[slot * QS_TC_MAX_WORDS + tid], 2), QS_TC_WORD_LEN);
         }
         __syncthreads();
+        if constexpr (G) {
+            if (guided && v0 < V) {
+                const uint32_t* arow = a.g.allow + (size_t)(*guide_state_word<G>()) * a.g.words;
+                deny |= ~(uint32_t)reinterpret_cast<const uint8_t*>(arow)[v0 >> 3] & 0xFFu;
+            }
+            if (guided) {   // the mask's zeros, on the element as loaded: in front of the bias, as the reference orders them
+#pragma unroll
+                for (int e = 0; e < 8; e++) x[e] = f2h(h2f(x[e]) + 0.0f);
+            }
+        }
         int ban = -1;
         if (tid < n_words) {
             const int ws[QS_TC_WORD_LEN] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
@@ -1086,8 +1149,8 @@ __global__ __launch_bounds__(256) void process_logits_kernel(typename LpArgsOf<C
         }
     }
 }
-// the kernel instantiation (<C>) follows the presence of a.c.deny
-int process_logits(const LpArgsC& a, int T, hipStream_t st) {
+// the kernel instantiation follows the presence of a.c.deny (<C>) and of a.g.allow (<C, G>)
+int process_logits(const LpArgsG& a, int T, hipStream_t st) {
     if (T == 0) return 0;
     if (a.stop_width < 0 || a.stop_width > QS_LP_MAX_STOP || a.nslots < 1 || a.rows_per_seq < 1 || a.j_base < 0 ||
         a.j_base + a.rows_per_seq - 1 > QS_LP_MAX_INFLIGHT)
@@ -1098,7 +1161,92 @@ int process_logits(const LpArgsC& a, int T, hipStream_t st) {
         return 0;
     }
     if (a.c.gen_cap < 1 || (int64_t)a.c.deny_words * 32 < a.V) return -1;
-    hipLaunchKernelGGL(process_logits_kernel<true>, grid, dim3(256), 0, st, a);
+    if (!a.g.allow) {
+        hipLaunchKernelGGL(process_logits_kernel<true>, grid, dim3(256), 0, st, static_cast<const LpArgsC&>(a));
+        return 0;
+    }
+    if (a.g.words % 4 || (int64_t)a.g.words * 32 < a.V || a.g.n_states < 1 || a.g.n_trans < 1) return -1;
+    hipLaunchKernelGGL((process_logits_kernel<true, true>), grid, dim3(256), 0, st, a);
+    return 0;
+}
+// Admission (outside the graph): one workgroup per state of a guide's CSR (row_ptr [n_states + 1], tokens ascending and distinct
+// per state, next states; validated by the host).  The allow row is assembled in LDS with LDS bit-sets and written with 16-byte
+// stores; a workgroup scan of the word popcounts gives the rank row; the state's transitions go to nxt[trans_base + ...] as arena
+// rows (state_base + next).  Rows are row_stride words apart (>= words, a multiple of 4); only `words` of each are written.
+#define QS_GUIDE_MAX_WORDS 8192   // 32 KB of LDS: vocabularies up to 262144
+__global__ __launch_bounds__(256) void guide_build_kernel(uint32_t* __restrict__ allow, int32_t* __restrict__ rank,
+                                                          int32_t* __restrict__ off, int32_t* __restrict__ nxt, int words,
+                                                          int row_stride, int V, int state_base, int trans_base, int n_trans,
+                                                          const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ tokens,
+                                                          const int32_t* __restrict__ next) {
+    extern __shared__ uint32_t s_row[];
+    __shared__ int s_sum[256];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    for (int i = tid; i < words; i += 256) s_row[i] = 0u;
+    __syncthreads();
+    const int lo = min(max(row_ptr[s], 0), n_trans), hi = min(max(row_ptr[s + 1], lo), n_trans);
+    for (int i = lo + tid; i < hi; i += 256) {
+        const int t = tokens[i];
+        if (t >= 0 && t < V) atomicOr(&s_row[t >> 5], 1u << (t & 31));
+        nxt[trans_base + i] = state_base + next[i];
+    }
+    __syncthreads();
+    uint32_t* arow = allow + (size_t)(state_base + s) * row_stride;
+    int32_t* rrow = rank + (size_t)(state_base + s) * row_stride;
+    for (int i = 4 * tid; i < words; i += 1024) *reinterpret_cast<u32x4*>(arow + i) = *reinterpret_cast<const u32x4*>(s_row + i);
+    // every thread owns `per` consecutive words (a multiple of 4): its popcount sum, a scan over the 256 sums, its rank words
+    const int per = ((words + 255) / 256 + 3) & ~3;
+    const int w0 = min(tid * per, words), w1 = min(w0 + per, words);
+    int sum = 0;
+    for (int i = w0; i < w1; i++) sum += __builtin_popcount(s_row[i]);
+    s_sum[tid] = sum;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {
+        const int v = tid >= d ? s_sum[tid - d] : 0;
+        __syncthreads();
+        s_sum[tid] += v;
+        __syncthreads();
+    }
+    int run = s_sum[tid] - sum;
+    for (int i = w0; i < w1; i += 4) {
+        int4 r;
+        r.x = run; run += __builtin_popcount(s_row[i]);
+        r.y = run; run += __builtin_popcount(s_row[i + 1]);
+        r.z = run; run += __builtin_popcount(s_row[i + 2]);
+        r.w = run; run += __builtin_popcount(s_row[i + 3]);
+        *reinterpret_cast<int4*>(rrow + i) = r;
+    }
+    if (tid == 0) off[state_base + s] = trans_base + lo;
+}
+int guide_build(uint32_t* allow, int32_t* rank, int32_t* off, int32_t* nxt, int words, int row_stride, int V, int state_base,
+                int trans_base, int n_states, const int32_t* row_ptr, const int32_t* tokens, const int32_t* next, int n_trans,
+                hipStream_t st) {
+    if (n_states == 0) return 0;
+    if (words < 4 || words % 4 || words > QS_GUIDE_MAX_WORDS || row_stride < words || row_stride % 4 || (int64_t)words * 32 < V)
+        return -1;
+    hipLaunchKernelGGL(guide_build_kernel, dim3(n_states), dim3(256), (size_t)words * 4, st, allow, rank, off, nxt, words,
+                       row_stride, V, state_base, trans_base, n_trans, row_ptr, tokens, next);
+    return 0;
+}
+// One thread per slot, as the token table's catch-up: a guided slot's state advances over the tokens committed since the last
+// catch-up, in order (k + 1 at most in the steady state, two round trips each).  Idempotent: see the INVARIANT above.
+__global__ void guide_catch_up_kernel(int B, int V, int32_t* __restrict__ gslot, LpGuide g, const int64_t* __restrict__ gen_tokens,
+                                      int gen_cap, const int32_t* __restrict__ gen_lens) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int4 gs = *reinterpret_cast<const int4*>(gslot + 4 * b);
+    if (!gs.w) return;
+    const int hi = min(gen_lens[b], gen_cap), lo = max(gs.y, 0);
+    if (hi <= lo) return;   // nothing new (or gen_lens went back: a freed slot; admission sets the state again)
+    int s = gs.x;
+    for (int i = lo; i < hi; i++) s = guide_next(g, V, s, gen_tokens[(size_t)b * gen_cap + i], gs.z);
+    gslot[4 * b] = s;
+    gslot[4 * b + 1] = hi;
+}
+int guide_catch_up(int B, int V, int32_t* gslot, const LpGuide& g, const int64_t* gen_tokens, int gen_cap,
+                   const int32_t* gen_lens, hipStream_t st) {
+    if (B == 0) return 0;
+    hipLaunchKernelGGL(guide_catch_up_kernel, dim3((B + 63) / 64), dim3(64), 0, st, B, V, gslot, g, gen_tokens, gen_cap, gen_lens);
     return 0;
 }
 // Admission (outside the graph): ONE workgroup builds the slot's deny row -- all ones where the request has allowed_token_ids,

@@ -1019,6 +1019,97 @@ def process_logits_constrained(logits, out, tok_table, repetition, frequency, pr
     return out
 
 
+# ------------------------------------------------------------------ token guides (include/qspec_hip.h, "token guides")
+MAX_GUIDE_WORDS = 8192   # words of an allow row the build kernel assembles in LDS: vocabularies up to 262144
+
+
+class TokenGuides:
+    """The device arena of the resident guides (allow / rank rows per state, offsets, transitions) and the per-slot guide state
+    gslot [num_slots, 4] = {state, g_len, miss state, guided}; all zero: no slot is guided.  Where a guide sits in the arena
+    is the caller's bookkeeping (spec_decode.guides.GuideArena)."""
+
+    def __init__(self, num_slots: int, vocab: int, device, max_states: int, max_transitions: int):
+        z = lambda *shape: torch.zeros(*shape, dtype=_I32, device=device)   # noqa: E731
+        self.num_slots, self.vocab, self.max_states, self.max_transitions = num_slots, vocab, int(max_states), int(max_transitions)
+        self.words = ((vocab + 31) // 32 + 3) // 4 * 4
+        if self.words > MAX_GUIDE_WORDS:
+            raise ValueError(f"vocabulary {vocab}: guides support at most {MAX_GUIDE_WORDS * 32} tokens")
+        self.allow, self.rank = z(self.max_states, self.words), z(self.max_states, self.words)
+        self.off, self.nxt = z(self.max_states), z(self.max_transitions)
+        self.gslot = z(num_slots, 4)
+
+    def arrays(self):
+        return (self.allow, self.rank, self.off, self.nxt, self.gslot)
+
+    def set_slot(self, slot: int, state: int = 0, miss: int = 0, guided: bool = False, g_len: int = 0) -> None:
+        self.gslot[slot].copy_(torch.tensor([state, g_len, miss, 1] if guided else [0, 0, 0, 0], dtype=_I32))
+
+
+def guide_build(tg: TokenGuides, state_base: int, trans_base: int, row_ptr, tokens, next_states, row_stride=None) -> None:
+    """Build the rows of one guide (numpy CSR, validated by the caller: spec_decode.guides.TokenFSM) at arena rows state_base ..
+    and transitions trans_base .. (admission time, outside any graph)."""
+    dev = tg.allow.device
+    S, N = int(row_ptr.shape[0]) - 1, int(tokens.shape[0])
+    if S < 1 or N < 1 or state_base < 0 or trans_base < 0 or state_base + S > tg.max_states or trans_base + N > tg.max_transitions:
+        raise ValueError(f"a guide of {S} states and {N} transitions at ({state_base}, {trans_base}) does not fit the arena "
+                         f"({tg.max_states} states, {tg.max_transitions} transitions)")
+    up = lambda a: torch.from_numpy(a.astype("int32")).to(dev)   # noqa: E731
+    rp, tk, nx = up(row_ptr), up(tokens), up(next_states)
+    stride = tg.allow.stride(0) if row_stride is None else int(row_stride)
+    _call("qspec_guide_build", _chk(tg.allow, "guide_allow", _I32), _chk(tg.rank, "guide_rank", _I32), _chk(tg.off, "guide_off", _I32),
+          _chk(tg.nxt, "guide_next", _I32), tg.words, stride, tg.vocab, tg.max_states, tg.max_transitions, int(state_base),
+          int(trans_base), S, N, _chk(rp, "row_ptr", _I32), _chk(tk, "tokens", _I32), _chk(nx, "next_states", _I32), _stream())
+    # (the staging tensors are freed behind the launch: the caching allocator reuses memory in stream order)
+
+
+def _guide_args(tg_arrays):
+    allow, rank, off, nxt, gslot = tg_arrays
+    if allow.dim() != 2 or rank.shape != allow.shape or off.numel() < allow.shape[0] or gslot.dim() != 2 or gslot.shape[1] != 4:
+        raise RuntimeError("the guide arrays are those of a TokenGuides")
+    return (_chk(allow, "guide_allow", _I32), _chk(rank, "guide_rank", _I32), _chk(off, "guide_off", _I32),
+            _chk(nxt, "guide_next", _I32)), _chk(gslot, "guide_slots", _I32), (allow.shape[1], allow.shape[0], nxt.numel())
+
+
+def guide_catch_up(guide_allow, guide_rank, guide_off, guide_next, guide_slots, vocab: int, gen_tokens, gen_lens):
+    """Advance the state of every guided slot over gen_tokens[slot][g_len .. gen_lens); g_len = gen_lens.  Idempotent."""
+    B = guide_slots.shape[0]
+    if gen_tokens.shape[0] < B or gen_lens.numel() < B:
+        raise RuntimeError("the per-slot arrays are shorter than guide_slots")
+    arena, gslot, sizes = _guide_args((guide_allow, guide_rank, guide_off, guide_next, guide_slots))
+    _call("qspec_guide_catch_up", gslot, B, int(vocab), *arena, *sizes, _chk(gen_tokens, "gen_tokens", _I64), gen_tokens.shape[1],
+          _chk(gen_lens, "gen_lens", _I32), _stream())
+
+
+def process_logits_guided(logits, out, tok_table, repetition, frequency, presence, min_tokens, gen_base, gen_lens, stop_ids,
+                          num_stop_ids, deny, meta, bias_ids, bias_vals, words, word_lens, tail, gen_tokens, guide_allow,
+                          guide_rank, guide_off, guide_next, guide_slots, draft_ids=None, rows_per_seq: int = 1, j_base: int = 0,
+                          slot_ids=None, active_lens=None):
+    """process_logits_constrained with the token guides in front of it, in the same launch: a row of a guided slot (guide_slots
+    [num_slots, 4]) is masked with the allow row of the state reached from the slot's state over the in-flight
+    draft_ids[0 .. j, slot], and gets an fp32 zero added to every element.  The guide arrays are those of a TokenGuides; a slot
+    whose guide_slots row is zero gets the bits of process_logits_constrained."""
+    V, B = logits.shape[1], tok_table.shape[0]
+    args = _process_logits_args(logits, out, tok_table, repetition, frequency, presence, min_tokens, gen_base, gen_lens, stop_ids,
+                                num_stop_ids, draft_ids, rows_per_seq, j_base, slot_ids, active_lens)
+    if deny.dim() != 2 or deny.shape[0] < B or deny.shape[1] * 32 < V:
+        raise RuntimeError("deny must be [num_slots, >= ceil(vocab / 32)]")
+    for t, shape, name in ((meta, (4,), "meta"), (bias_ids, (MAX_LOGIT_BIAS,), "bias_ids"), (bias_vals, (MAX_LOGIT_BIAS,), "bias_vals"),
+                           (words, (MAX_BAD_WORDS, MAX_BAD_WORD_LEN), "words"), (word_lens, (MAX_BAD_WORDS,), "word_lens"),
+                           (tail, (MAX_BAD_WORD_LEN - 1,), "tail")):
+        if t.shape[0] < B or tuple(t.shape[1:]) != shape:
+            raise RuntimeError(f"{name} must be [num_slots, {', '.join(str(d) for d in shape)}]")
+    if gen_tokens.dim() != 2 or gen_tokens.shape[0] < B:
+        raise RuntimeError("gen_tokens must be [num_slots, capacity]")
+    if guide_slots.shape[0] < B or guide_allow.shape[1] * 32 < V:
+        raise RuntimeError("guide_slots must cover the slots and the allow rows the vocabulary")
+    arena, gslot, sizes = _guide_args((guide_allow, guide_rank, guide_off, guide_next, guide_slots))
+    _call("qspec_process_logits_guided", *args, _chk(deny, "deny", _I32), deny.shape[1], _chk(meta, "meta", _I32),
+          _chk(bias_ids, "bias_ids", _I32), _chk(bias_vals, "bias_vals", _F32), _chk(words, "words", _I32),
+          _chk(word_lens, "word_lens", _I32), _chk(tail, "tail", _I32), _chk(gen_tokens, "gen_tokens", _I64),
+          gen_tokens.shape[1], *arena, gslot, *sizes, _stream())
+    return out
+
+
 def typical_acceptance_sample(target_with_bonus_probs, bonus_token_ids, draft_token_ids, posterior_threshold: float,
                               posterior_alpha: float, out_tokens, accepted, recovered, counters=None, workspace=None,
                               active_lens=None):

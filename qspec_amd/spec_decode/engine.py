@@ -82,12 +82,14 @@ class QSpecEngine:
     def __init__(self, model: QuarotLlamaForCausalLM, num_speculative_tokens: int = 3, max_batch: int = 4,
                  max_model_len: int = 1024, block_size: int = 16, max_new_tokens: int = 1024, use_graph: bool = True,
                  seed: int = 0, num_blocks: Optional[int] = None, acceptance_sampler=None, kv_cache_dtype: str = "auto",
-                 kv_scales=None, num_cpu_blocks: int = 0):
+                 kv_scales=None, num_cpu_blocks: int = 0, guide_states: int = 1024, guide_transitions: int = 1 << 24):
         """kv_cache_dtype: "auto" (fp16 cache) or "fp8" / "fp8_e4m3" (one e4m3 byte per element, half the cache bytes;
         include/qspec_hip.h, "FP8 KV cache").  kv_scales: per layer (k_scale, v_scale) for the fp8 cache, kept on THIS engine
         and handed to every forward (the model, which other engines may share, is not touched); None keeps the model's
         (read from the checkpoint) or 1.0.  num_cpu_blocks: blocks of the pinned host cache swap_out / swap_in move KV blocks to
-        and from (initialize_cache's second number); 0 allocates nothing."""
+        and from (initialize_cache's second number); 0 allocates nothing.  guide_states / guide_transitions: the capacity of
+        the guide arena (guided decoding: resident automaton states and transitions over all resident guides; at Llama-3's
+        vocabulary a state costs 32 KB and a transition 4 B); allocated with the first guided request, never before."""
         if kv_cache_dtype not in ("auto", "fp8", "fp8_e4m3"):
             raise ValueError(f"kv_cache_dtype {kv_cache_dtype!r}: 'auto', 'fp8' or 'fp8_e4m3'")
         self.kv_cache_dtype = "auto" if kv_cache_dtype == "auto" else "fp8"
@@ -191,9 +193,10 @@ class QSpecEngine:
         # ---- what the requests' SamplingParams become on the device (slot_sampling.py) and the mode level the occupied slots ask
         # for: 0 greedy -- the cycle above (fused lm_head + softmax); 1 sampling -- EVERY row goes through ops.sample_top_k_top_p;
         # 2 logit processors -- + the token-table catch-up and the logits pre-pass; 3 token constraints -- the pre-pass's constrained
-        # entry (same launches).  One captured cycle per level a batch has asked for, keyed (level, "full"), or (level, "draft"):
-        # the fallback, the proposer alone with the verify pass eager.  Every other batch replays what it always did.
-        self.sampling = SlotSampling(B, k, V, dev)
+        # entry (same launches); 4 token guides -- its guided entry plus the guide catch-up at the head of the cycle.  One captured
+        # cycle per level a batch has asked for, keyed (level, "full"), or (level, "draft"): the fallback, the proposer alone with
+        # the verify pass eager.  Every other batch replays what it always did.
+        self.sampling = SlotSampling(B, k, V, dev, guide_states, guide_transitions)
         self._level = 0
         self._graphs: dict = {}
         # the sampling front end's histogram workspaces (draft / non-speculative rows, verify rows), zero-filled here --
@@ -206,12 +209,13 @@ class QSpecEngine:
         self._prefill_scratch: Optional[Scratch] = None
 
     # names the benchmark, scripts and tests read: whole-cycle graph per level, draft-only fallback, modes, state of self.sampling
-    _graph, _graph_s, _graph_p, _graph_c = (property(lambda self, lv=lv: self._graphs.get((lv, "full"))) for lv in range(4))
+    _graph, _graph_s, _graph_p, _graph_c, _graph_g = (property(lambda self, lv=lv: self._graphs.get((lv, "full"))) for lv in range(5))
     _graph_draft = property(lambda self: self._graphs.get((0, "draft")))
-    _mode_sampling, _mode_processing, _mode_constrained = (property(lambda self, lv=lv: self._level >= lv) for lv in (1, 2, 3))
-    seq_seeded, lp_gen_base, tok_table, counted_len, proc_logits_d, proc_logits_v, tc, _lp_host, _tc_host = (
+    _mode_sampling, _mode_processing, _mode_constrained, _mode_guided = (
+        property(lambda self, lv=lv: self._level >= lv) for lv in (1, 2, 3, 4))
+    seq_seeded, lp_gen_base, tok_table, counted_len, proc_logits_d, proc_logits_v, tc, _lp_host, _tc_host, tg, guide_arena = (
         property(lambda self, n=n: getattr(self.sampling, n)) for n in
-        "seq_seeded lp_gen_base tok_table counted_len proc_logits_d proc_logits_v tc _lp_host _tc_host".split())
+        "seq_seeded lp_gen_base tok_table counted_len proc_logits_d proc_logits_v tc _lp_host _tc_host tg guide_arena".split())
 
     # the embedding lookups of the cycle's four forwards ride in the bookkeeping launches in front of them (5 launches less)
     EMBED_IN_BOOKKEEPING = os.environ.get("QSPEC_EMBED_IN_BOOKKEEPING", "1") != "0"
@@ -536,7 +540,7 @@ class QSpecEngine:
                 fused_greedy: bool = False, argmax: bool = False) -> None:
         """THE sampling front end -- the first token, the non-speculative step, every draft step and the verify pass come through
         here: lm_head -> the bench-only hook -> from level 2 on the logits pre-pass (self._process, out of place: the raw logits
-        stay in scratch.logits; level 3: its constrained entry) -> ops.sample_top_k_top_p over EVERY row (greedy rows take the
+        stay in scratch.logits; level 3: its constrained entry, level 4: its guided entry) -> ops.sample_top_k_top_p over EVERY row (greedy rows take the
         argmax there; min_p from level 2 on), or with `argmax` ops.softmax_argmax.  probs [T, V] fp32 is the
         PROCESSED distribution: what the rejection sampler must see.  rows: the per-row arrays (SlotSampling.draft_rows /
         verify_rows / gathered_rows); row t belongs to sequence t // rows_per_seq and is position j_base + t % rows_per_seq of
@@ -550,7 +554,7 @@ class QSpecEngine:
             hook(logits)
         if level >= 2:
             logits = self._process(logits, rows.proc_out, rows_per_seq, j_base, draft_ids, active_lens, slot_ids=rows.slot_ids,
-                                   constrained=level == 3)
+                                   constrained=level >= 3, **({"guided": True} if level == 4 else {}))
         if argmax:
             ops.softmax_argmax(logits, probs, token)
         else:
@@ -774,7 +778,7 @@ class QSpecEngine:
                             seed: Optional[int] = None, min_p: float = 0.0, presence_penalty: float = 0.0,
                             frequency_penalty: float = 0.0, repetition_penalty: float = 1.0, min_tokens: int = 0,
                             stop_token_ids: Sequence[int] = (), logit_bias=None, allowed_token_ids=None,
-                            bad_words_token_ids=None) -> None:
+                            bad_words_token_ids=None, guide=None) -> None:
         """The request in `slot` samples with these parameters (vllm/sampling_params.py; temperature < 1e-5 = greedy, for
         which vLLM itself resets top_k / top_p).  seed (SamplingParams.seed, taken mod 2^64): the request's draws depend
         on it and its own positions only; a greedy request makes no draws and ignores it.  Uploaded only when they
@@ -790,16 +794,24 @@ class QSpecEngine:
         words matched against the request's OUTPUTS (in flight included), never its prompt.  Like the penalties they are set
         BEFORE admission.  Refused with ValueError, nothing enqueued: an id outside the vocabulary, an empty allowed set or
         bad word, a cap exceeded, a non-finite bias, an occupied slot, and a request that can never emit anything (every
-        allowed token is a single-token bad word -- or, with min_tokens, a stop id)."""
+        allowed token is a single-token bad word -- or, with min_tokens, a stop id).
+        guide (guided decoding: a guides.TokenFSM, e.g. TokenFSM.from_guide(processor._guide, vocab)): in front of everything
+        above, every token the guide's state does not allow is set to -inf and every element of the row gets the fp32 zero of the
+        reference's mask (outlines_logits_processors.py:34-93); the state is the guide's initial state advanced over the
+        request's OUTPUTS, in flight included, never its prompt.  Set BEFORE admission.  Guides are shared by object identity:
+        requests that bring the same TokenFSM use one resident copy.  Refused with ValueError, nothing enqueued: not a TokenFSM,
+        another vocabulary, an occupied slot, no room in the guide arena (guide_states / guide_transitions) beside the guides in
+        use.  A row a guide leaves without a finite logit follows the rule of the constraints: token 0 is emitted."""
         self.sampling.set(slot, temperature, top_k, top_p, seed, min_p, presence_penalty, frequency_penalty, repetition_penalty,
                           min_tokens, stop_token_ids, logit_bias, allowed_token_ids, bad_words_token_ids,
-                          occupied=not self._is_empty(slot))
+                          occupied=not self._is_empty(slot), guide=guide)
 
     def _process(self, logits, out, rows_per_seq: int, j_base: int, draft_ids, active_lens, slot_ids=None,
-                 constrained: Optional[bool] = None):
+                 constrained: Optional[bool] = None, guided: Optional[bool] = None):
         """The logits pre-pass of the front end (tests wrap it on the instance: it is looked up at call time)."""
         return self.sampling.process(logits, out, rows_per_seq, j_base, draft_ids, active_lens, self.gen_tokens, self.gen_lens,
-                                     slot_ids=slot_ids, constrained=self._level == 3 if constrained is None else constrained)
+                                     slot_ids=slot_ids, constrained=self._level >= 3 if constrained is None else constrained,
+                                     guided=self._level == 4 if guided is None else guided)
 
     def set_block_table(self, slot: int, blocks: Sequence[int]) -> None:
         """The scheduler's block table of the request in `slot` (vLLM SequenceGroupMetadata.block_tables); it must
@@ -870,6 +882,8 @@ class QSpecEngine:
         self._snapshot()
         if self._level >= 2:   # the tokens committed since the last catch-up enter the table (idempotent: slot_sampling.py)
             self.sampling.catch_up(self.gen_tokens, self.gen_lens)
+        if self._level == 4:   # ... and the guided slots' states advance over them (idempotent in the same way)
+            self.sampling.guide_catch_up(self.gen_tokens, self.gen_lens)
 
     def _cycle_body(self):
         self._cycle_head()
@@ -977,6 +991,8 @@ class QSpecEngine:
         level = self.sampling.level(self.active_slots())
         if level >= 2:
             self.sampling.catch_up(self.gen_tokens, self.gen_lens)
+        if level == 4:
+            self.sampling.guide_catch_up(self.gen_tokens, self.gen_lens)
         self._sample(level, self.sampling.draft_rows(), hs, self.scratch_draft, self.draft_probs_kbv[0], self.draft_ids_kb[0],
                      base_pos=self.seq_lens, active_lens=self.eff_lens, workspace=self._sample_ws_d, argmax=level == 0)
         self.out_tokens.fill_(-1)

@@ -12,7 +12,14 @@ Three layers, each neutral -- and the last two unallocated -- until a request as
     gen_lens alone, so the engine's recover() -- which restores gen_lens to its value at the start of the failed cycle, i.e.
     to counted_len -- re-runs it without double counting.
   3 token constraints (include/qspec_hip.h, "token constraints"): logit_bias, allowed_token_ids, bad words in an
-    ops.TokenConstraints (a deny bitmask, a sorted bias list, the multi-token words, the pre-admission tail)."""
+    ops.TokenConstraints (a deny bitmask, a sorted bias list, the multi-token words, the pre-admission tail).
+  4 token guides (include/qspec_hip.h, "token guides"): guided decoding, a guides.TokenFSM per slot.  The resident guides sit
+    in an ops.TokenGuides arena (allocated with the first guided request) placed by a guides.GuideArena: one copy per guide
+    object, reference-counted by the slots.  gslot[b] = {state, g_len, miss, guided}: the state after g_len of
+    gen_tokens[b][:gen_lens[b]].  INVARIANT (as counted_len's): the guide catch-up is driven by gen_lens alone -- it walks
+    gen_tokens[b][g_len .. gen_lens) and sets g_len = gen_lens -- so recover(), which restores gen_lens to its value at the
+    start of the failed cycle, i.e. to g_len, re-runs it without walking a token twice.  The outputs a re-admitted request had
+    before its admission are walked on the host at admission (g_len = 0)."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -21,6 +28,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .. import ops
+from .guides import GuideArena, TokenFSM
 
 
 # The per-row arrays of one sampler call.  slot_ids: the slot of each sequence (None: sequence i is slot i); proc_out: where the
@@ -31,8 +39,13 @@ Rows = namedtuple("Rows", "temp topk topp minp seeds seeded slot_ids proc_out")
 class SlotSampling:
     _LP_NEUTRAL = (0.0, 0.0, 0.0, 1.0, 0, ())   # min_p, presence, frequency, repetition, min_tokens, stop ids
 
-    def __init__(self, B: int, k: int, vocab_size: int, device):
+    def __init__(self, B: int, k: int, vocab_size: int, device, guide_states: int = 1024, guide_transitions: int = 1 << 24):
         self.B, self.k, self.vocab_size, self.device = B, k, vocab_size, torch.device(device)
+        if int(guide_states) < 1 or int(guide_transitions) < 1:
+            raise ValueError("guide_states / guide_transitions must be >= 1")
+        self.guide_states, self.guide_transitions = int(guide_states), int(guide_transitions)
+        self._g_host = None       # per slot None, or its TokenFSM; None until first used
+        self.tg = self.guide_arena = None
         T, dev = B * (k + 1), self.device
         self.samp_temp = torch.zeros(B, dtype=torch.float32, device=dev)
         self.samp_topk = torch.full((B,), -1, dtype=torch.int32, device=dev)
@@ -62,11 +75,17 @@ class SlotSampling:
     def constraints_on(self, occupied_slots: Sequence[int]) -> bool:
         return self._tc_host is not None and any(self._tc_host[b] is not None for b in occupied_slots)
 
+    def guides_on(self, occupied_slots: Sequence[int]) -> bool:
+        return self._g_host is not None and any(self._g_host[b] is not None for b in occupied_slots)
+
     def processing_on(self, occupied_slots: Sequence[int]) -> bool:   # a non-neutral logit processor, or a token constraint
         return self.constraints_on(occupied_slots) or (
             self._lp_host is not None and any(self._lp_host[b] != self._LP_NEUTRAL for b in occupied_slots))
 
-    def level(self, occupied_slots: Sequence[int]) -> int:   # 0 greedy, 1 sampling, 2 logit processors, 3 token constraints
+    def level(self, occupied_slots: Sequence[int]) -> int:
+        """0 greedy, 1 sampling, 2 logit processors, 3 token constraints, 4 token guides"""
+        if self.guides_on(occupied_slots):
+            return 4
         return 3 if self.constraints_on(occupied_slots) else 2 if self.processing_on(occupied_slots) else \
             int(self.sampling_on(occupied_slots))
 
@@ -92,7 +111,7 @@ class SlotSampling:
     def set(self, slot: int, temperature: float = 0.0, top_k: int = -1, top_p: float = 1.0, seed: Optional[int] = None,
             min_p: float = 0.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, repetition_penalty: float = 1.0,
             min_tokens: int = 0, stop_token_ids: Sequence[int] = (), logit_bias=None, allowed_token_ids=None,
-            bad_words_token_ids=None, occupied: bool = False) -> None:
+            bad_words_token_ids=None, occupied: bool = False, guide: Optional[TokenFSM] = None) -> None:
         """QSpecEngine.set_sampling_params (its docstring is the contract).  occupied: a request sits in the slot."""
         stop = tuple(int(t) for t in stop_token_ids)
         vals = (float(min_p), float(presence_penalty), float(frequency_penalty), float(repetition_penalty))
@@ -108,6 +127,7 @@ class SlotSampling:
             raise ValueError(f"min_tokens {min_tokens} must be >= 0")
         want_tc = self._validate_constraints(slot, logit_bias, allowed_token_ids, bad_words_token_ids,
                                              stop if int(min_tokens) > 0 else (), occupied)
+        self._validate_guide(slot, guide, occupied)
         if temperature < 1e-5:   # (min_p is reset for greedy requests, sampling_params.py:344; the rest applies to them too)
             temperature, top_k, top_p, seed = 0.0, -1, 1.0, None
             vals = (0.0,) + vals[1:]
@@ -145,6 +165,8 @@ class SlotSampling:
             else:
                 ops.token_constraints_set(self.tc, slot, dict(want_tc[0]), want_tc[1], [list(w) for w in want_tc[2]])
             self._tc_host[slot] = want_tc
+        if guide is not self._guide(slot):
+            self._set_guide(slot, guide)
         want_seed = None if seed is None else int(seed) % (1 << 64)
         if self._seed_host[slot] != want_seed:
             self.seq_seed[slot] = 0 if want_seed is None else want_seed - (1 << 64) * (want_seed >= 1 << 63)
@@ -168,15 +190,18 @@ class SlotSampling:
         min_p, pres, freq, rep, min_tokens, stop = self._lp(src)
         bias, allowed, words = self._tc(src) or ((), None, ())
         self.set(dst, temp, topk, topp, None if seed is None else (seed + seed_add) % (1 << 64), min_p, pres, freq, rep, min_tokens,
-                 stop, dict(bias), allowed, [list(w) for w in words], occupied=occupied)
+                 stop, dict(bias), allowed, [list(w) for w in words], occupied=occupied, guide=self._guide(src))
 
     def fork(self, src: int, dst: int) -> None:
         """Everything slot `src` holds here copied to the EMPTY slot `dst`: the parameters (same seed: a fork continues its
         parent's draws until the two diverge), the token-table row with counted_len and the output base, the pre-admission
-        tail of the token constraints.  Plain copies: forking is not on the step's critical path."""
+        tail of the token constraints, the guide reference with its state and g_len.  Plain copies: forking is not on the
+        step's critical path."""
         self.clone_params(src, dst)
         if self._lp_host is None:
             return
+        if self._guide(src) is not None:   # (the same resident guide: the same arena rows)
+            self.tg.gslot[dst].copy_(self.tg.gslot[src])
         self.tok_table[dst].copy_(self.tok_table[src])
         self.counted_len[dst] = self.counted_len[src]
         self.lp_gen_base[dst] = self.lp_gen_base[src]
@@ -234,6 +259,56 @@ class SlotSampling:
             raise ValueError(f"slot {slot} is occupied: token constraints are set before the request is admitted")
         return want
 
+    def _guide(self, slot: int) -> Optional[TokenFSM]:
+        return None if self._g_host is None else self._g_host[slot]
+
+    def _validate_guide(self, slot: int, guide, occupied: bool) -> None:
+        """ValueError, nothing enqueued: not a TokenFSM, another vocabulary, an occupied slot, no room in the arena."""
+        if guide is self._guide(slot):
+            return
+        if occupied:
+            raise ValueError(f"slot {slot} is occupied: a guide is set before the request is admitted")
+        if guide is None:
+            return
+        if not isinstance(guide, TokenFSM):
+            raise ValueError("guide must be a TokenFSM (guides.TokenFSM.from_guide lowers a guide object)")
+        if guide.vocab != self.vocab_size:
+            raise ValueError(f"the guide was lowered for a vocabulary of {guide.vocab}, the model has {self.vocab_size}")
+        arena = self.guide_arena or GuideArena(self.guide_states, self.guide_transitions)
+        if arena.resident(guide) is None:
+            old = self._guide(slot)   # (the slot's present guide is released first: its room counts when it has no other user)
+            r = arena.resident(old) if old is not None else None
+            if r is not None:
+                r.refs -= 1
+            try:
+                arena.plan(guide)
+            finally:
+                if r is not None:
+                    r.refs += 1
+
+    def _set_guide(self, slot: int, guide: Optional[TokenFSM]) -> None:
+        """Release the slot's guide, take a reference to the new one (built into the arena when it is not resident)."""
+        old = self._guide(slot)
+        if old is not None:
+            self.guide_arena.release(old)
+            self._g_host[slot] = None
+        if guide is None:
+            self.tg.set_slot(slot)
+            return
+        self._ensure_processing()
+        if self.tc is None:   # the guided entry rides on the constrained one: its (all-zero) arrays exist
+            self.tc = ops.TokenConstraints(self.B, self.vocab_size, self.device)
+            self._tc_host = [None] * self.B
+        if self.tg is None:
+            self.tg = ops.TokenGuides(self.B, self.vocab_size, self.device, self.guide_states, self.guide_transitions)
+            self.guide_arena = GuideArena(self.guide_states, self.guide_transitions)
+            self._g_host = [None] * self.B
+        r, fresh = self.guide_arena.acquire(guide)
+        if fresh:
+            ops.guide_build(self.tg, r.state_base, r.trans_base, guide.row_ptr, guide.tokens, guide.next_states)
+        self._g_host[slot] = guide
+        self.tg.set_slot(slot, r.state_base + guide.initial, r.state_base + guide.miss, guided=True)
+
     def _lp_needs(self, slot: int) -> bool:
         """The slot keeps token counts: one of its penalties is non-neutral (in fp16, as the kernels read it)."""
         _, pres, freq, rp, _, _ = self._lp(slot)
@@ -266,6 +341,10 @@ class SlotSampling:
         base = len(tokens) - npt
         if self._tc(slot) is not None:
             ops.token_constraints_set_tail(self.tc, slot, list(tokens)[npt:])
+        g = self._guide(slot)
+        if g is not None:   # the outputs the request already has are walked here; gen_tokens starts empty: g_len = 0
+            base_state = self.guide_arena.resident(g).state_base
+            self.tg.set_slot(slot, base_state + g.advance(g.initial, list(tokens)[npt:]), base_state + g.miss, guided=True)
         if self._gen_base_host[slot] != base:
             self.lp_gen_base[slot] = base
             self._gen_base_host[slot] = base
@@ -278,13 +357,19 @@ class SlotSampling:
         """The tokens committed since the last catch-up enter the table (idempotent: see the module docstring)."""
         ops.logit_table_catch_up(self.tok_table, self.counted_len, self.lp_need, gen_tokens, gen_lens)
 
+    def guide_catch_up(self, gen_tokens, gen_lens) -> None:
+        """The state of every guided slot advances over the tokens committed since (idempotent: see the module docstring)."""
+        ops.guide_catch_up(*self.tg.arrays(), self.vocab_size, gen_tokens, gen_lens)
+
     def process(self, logits, out, rows_per_seq: int, j_base: int, draft_ids, active_lens, gen_tokens, gen_lens, slot_ids=None,
-                constrained: bool = False):
-        """The logits pre-pass in front of a sampler call (ops.process_logits, or its constrained entry: same launches)."""
+                constrained: bool = False, guided: bool = False):
+        """The logits pre-pass in front of a sampler call (ops.process_logits, or its constrained / guided entry: same launches)."""
         T = logits.shape[0]
         shared = (logits, out[:T], self.tok_table, self.lp_rep, self.lp_freq, self.lp_pres, self.lp_min_tokens, self.lp_gen_base,
                   gen_lens, self.lp_stop_ids, self.lp_n_stop)
         rows = dict(draft_ids=draft_ids, rows_per_seq=rows_per_seq, j_base=j_base, slot_ids=slot_ids, active_lens=active_lens)
+        if guided:
+            return ops.process_logits_guided(*shared, *self.tc.arrays(), gen_tokens, *self.tg.arrays(), **rows)
         if constrained:
             return ops.process_logits_constrained(*shared, *self.tc.arrays(), gen_tokens, **rows)
         return ops.process_logits(*shared, **rows)

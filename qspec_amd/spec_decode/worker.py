@@ -53,6 +53,7 @@ import torch
 
 from ..model import CONFIGS, QuarotLlamaConfig, QuarotLlamaForCausalLM
 from .engine import QSpecEngine
+from .guides import TokenFSM
 from .metrics import AsyncMetricsCollector, SpecDecodeWorkerMetrics
 
 VLLM_INVALID_TOKEN_ID = -1       # vllm/sequence.py:29
@@ -88,6 +89,9 @@ class SamplingParams:
     allowed_token_ids: Optional[List[int]] = None
     bad_words_token_ids: Optional[List[List[int]]] = None
     logits_processors: Optional[List[Any]] = None
+    # guided decoding: a guides.TokenFSM (vLLM's guided_decoding arrives lowered to an Outlines processor in logits_processors,
+    # which the worker recognises; the worker has no tokenizer, so its own field takes the finished automaton)
+    guided_fsm: Optional[Any] = None
     # parallel sampling: best_of (default: n) sequences are sampled from one prompt pass; beam search is refused
     n: int = 1
     best_of: Optional[int] = None
@@ -783,6 +787,7 @@ class SpecDecodeWorker:
                 extra = {} if seed is None else {"seed": seed}
                 lp = self._logit_processor_args(sp)
                 lp.update(self._token_constraint_args(sp))
+                lp.update(self._guide_args(sp, getattr(getattr(self, "model_config", None), "vocab_size", None)))
                 extra.update(lp)
                 if not r:   # (they belong to the request: a resumed one has them since its first chunk)
                     self.engine.set_sampling_params(b, getattr(sp, "temperature", 0.0) or 0.0, getattr(sp, "top_k", -1) or -1,
@@ -898,6 +903,44 @@ class SpecDecodeWorker:
         if words:
             out["bad_words_token_ids"] = [list(w) for w in dict.fromkeys(words)]
         return out
+
+    @staticmethod
+    def _guide_args(sp, vocab: Optional[int]) -> Dict[str, Any]:
+        """The `guide` keyword of engine.set_sampling_params for a request, EMPTY when it has none.  Sources: the worker's own
+        `guided_fsm` field (a TokenFSM) and the processor the reference's engine lowers guided_decoding to, at index 0 of
+        logits_processors (llm_engine.py:1950-2009; outlines_logits_processors.py:34-93), recognised by name and attributes --
+        nothing is imported: an object whose class is named RegexLogitsProcessor or JSONLogitsProcessor, or any processor with
+        a `_guide` that TokenFSM.from_guide accepts (its `_fsm_state`, the reference's hash chain, is ignored: the state is
+        rebuilt from the request's outputs).  NotImplementedError naming the class, never silence: a guided processor whose
+        guide is not a finite automaton over int states (CFGLogitsProcessor, CFGState), more than one guide on a request, and
+        a `guided_decoding` that arrives un-lowered (there is no tokenizer here to lower it with)."""
+        if sp is None:
+            return {}
+        if getattr(sp, "guided_decoding", None) is not None:
+            raise NotImplementedError(f"SamplingParams.guided_decoding = {type(sp.guided_decoding).__name__} arrived un-lowered: "
+                                      "this worker has no tokenizer; hand it the lowered processor (the engine's "
+                                      "_build_logits_processors) or a TokenFSM in guided_fsm")
+        found = []
+        own = getattr(sp, "guided_fsm", None)
+        if own is not None:
+            if not isinstance(own, TokenFSM):
+                raise ValueError("guided_fsm must be a TokenFSM")
+            found.append(own)
+        for proc in (getattr(sp, "logits_processors", None) or ()):
+            name, guide = type(proc).__name__, getattr(proc, "_guide", None)
+            if name == "CFGLogitsProcessor" or type(guide).__name__ == "CFGGuide":
+                raise NotImplementedError(f"{name}: a context-free-grammar guide is not a finite automaton over int states")
+            if name not in ("RegexLogitsProcessor", "JSONLogitsProcessor") and guide is None:
+                continue
+            if guide is None or vocab is None:
+                raise NotImplementedError(f"{name}: no `_guide` to lower" if guide is None else f"{name}: the vocabulary is unknown")
+            try:
+                found.append(TokenFSM.from_guide(guide, int(vocab)))
+            except TypeError as exc:
+                raise NotImplementedError(f"{name}: {exc}") from exc
+        if len(set(id(f) for f in found)) > 1:
+            raise NotImplementedError("more than one guide on one request")
+        return {"guide": found[0]} if found else {}
 
     def _decode_slots(self, sgml) -> List[int]:
         """Engine slots of a decode batch in request order; refreshes block tables (the engine uploads a table only when
